@@ -18,13 +18,19 @@ under ``torch.distributed.run`` before touching the GPU):
 * ``--mode rows``: the row split with the fit replicated per rank (strong);
 * ``--mode replicas``: every rank its own 10 000 draws (weak; labelled as such).
 
-The headline ``value`` comes from a timed pass with per-launch profiling OFF; the
+The headline ``value`` comes from a timed pass with per-launch profiling OFF.  A plain run
+does only that: set up, warm up, time ``--steps`` calls, write the last call's result if
+``--dump-outputs DIR`` is given (``DIR/<name>.npy``, float32; the inputs and the Philox
+counters are seeded, so equal arguments give equal inputs in every run) and print the
+result line.  Everything else is behind ``--full``: the
 roofline object and the per-kernel table come from a second pass of the same
 workload with HIP events around every engine launch (npfn_prof_*; the AR fits then run
 in order on the main stream, so each event pair times its launch alone); FLOPs and bytes
 are algorithmic.  ``--profile-all`` profiles the warmup and headline passes
-too: the form the rocprofv3 kernel-stats run uses, so its durations match the live ones.  ``cpu_baseline`` runs the CPU oracle (numpy
-restatement, oracle/) on rank 0 at N=1 on a bounded sample (see its "sample").
+too: the form the rocprofv3 kernel-stats run uses, so its durations match the live ones.
+``cpu_baseline`` (``--full``, unless ``--no-cpu-baseline``) runs the CPU oracle (numpy
+restatement, oracle/) on rank 0 at N=1 on a bounded sample (see its "sample"); at N > 1
+``--full`` also adds the per-rank phase split and, beside the EP line, the row-split form.
 """
 
 from __future__ import annotations
@@ -70,7 +76,14 @@ def parse():
     ap.add_argument("--samples", type=int, default=10_000)
     ap.add_argument("--sims", type=int, default=1000)
     ap.add_argument("--dim", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the profiled pass "
+                         "(roofline, per-kernel table, per-rank split), the row-split form beside the EP line at "
+                         "N > 1, the CPU baseline (c2, one GPU), c4's profiled run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the arrays the last timed call returned as DIR/<name>.npy "
+                         "(float32; at most 64 MB in all, a fixed seeded sample of the elements of a larger result)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--preprocessing", choices=["ensemble", "none", "quantile", "quantile+power"], default="ensemble",
                     help="per-estimator preprocessing (Engine.set_preprocessing); default: tabpfn's regressor ensemble")
     ap.add_argument("--cpu-rows", type=int, default=256, help="query rows per step in the CPU-baseline sample")
@@ -82,6 +95,29 @@ def parse():
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic.json"),
                     help="per-launch HBM bytes of the dominant kernel from a rocprofv3 --pmc run")
     return ap.parse_args()
+
+
+DUMP_MAX_BYTES = 64 * 10**6
+
+
+def dump_outputs(directory: str, arrays: dict) -> None:
+    """--dump-outputs: every tensor of ``arrays`` as ``directory/<name>.npy`` in float32 (float64
+    stays float64).  The budget of DUMP_MAX_BYTES is shared equally; an array over its share is
+    cut to a sample of its elements (flattened, in order) at positions drawn with a fixed seed,
+    the same positions in every run."""
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(1, len(arrays)) - 4096  # .npy header
+    for name, t in arrays.items():
+        if isinstance(t, torch.Tensor):
+            t = t.detach().cpu()
+            a = (t if t.dtype == torch.float64 else t.float()).numpy()
+        else:
+            a = np.asarray(t)
+            a = a if a.dtype == np.float64 else a.astype(np.float32)
+        if a.nbytes > share:
+            keep = share // a.itemsize
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
 
 
 def gl_task(D: int, n: int, seed: int = 0):
@@ -301,6 +337,8 @@ def run_notebook(args, dev):
         "note": "notebook_*_s are the reference notebook's published seconds (cell 8; hardware not stated): "
                 "context, not a target",
     }
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"samples": out})  # the last timed call: sample_batched at 50 obs
     print(json.dumps(line), flush=True)
 
 
@@ -385,6 +423,8 @@ def run_sampling_comparison(args, dev):
         "note": "published_s are the reference notebook's printed seconds at N = 10 (its device line says cpu): "
                 "context, not a target",
     }
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"samples": sb})  # the last timed call: strategy B at the largest N
     print(json.dumps(line), flush=True)
 
 
@@ -478,7 +518,7 @@ def run_c4(args, dev):
             run_once(0)
         runs = []
         for i in range(max(1, min(args.steps, 3))):
-            total, _ = run_once(0)
+            total, post = run_once(0)
             runs.append((total, dict(timers), dict(counts), list(marks), sim_t["s"]))
         best = min(runs, key=lambda r: r[0])
         total, tm, cnt, mk, sim_s = best
@@ -488,22 +528,22 @@ def run_c4(args, dev):
             a, b = bounds[r], bounds[r + 1]
             d = {k: round((b.get(k, 0.0) - a.get(k, 0.0)) * 1e3, 2) for k in b}
             per_round.append(d)
-        # profiled run: the classifier and regressor engines' kernel tables
-        prof_on["on"] = True
-        engines["classifier"].clear()
-        engines["regressor"].clear()
-        run_once(0)
-        prof = {}
-        for kind, engs in engines.items():
-            agg = {}
-            for eng in engs:
-                for e in eng.prof_read():
-                    a = agg.setdefault(e["name"], {"name": e["name"], "launches": 0, "ms": 0.0, "flops": 0.0,
-                                                  "bytes": 0.0})
-                    for key in ("launches", "ms", "flops", "bytes"):
-                        a[key] += e[key]
-                eng.prof_enable(False)
-            prof[kind] = list(agg.values())
+        prof = {"classifier": [], "regressor": []}
+        if args.full:  # one more, profiled run: the classifier and regressor engines' kernel tables
+            prof_on["on"] = True
+            engines["classifier"].clear()
+            engines["regressor"].clear()
+            run_once(0)
+            for kind, engs in engines.items():
+                agg = {}
+                for eng in engs:
+                    for e in eng.prof_read():
+                        a = agg.setdefault(e["name"], {"name": e["name"], "launches": 0, "ms": 0.0, "flops": 0.0,
+                                                      "bytes": 0.0})
+                        for key in ("launches", "ms", "flops", "bytes"):
+                            a[key] += e[key]
+                    eng.prof_enable(False)
+                prof[kind] = list(agg.values())
     finally:
         for obj, name, orig in saved:
             setattr(obj, name, orig)
@@ -539,8 +579,10 @@ def run_c4(args, dev):
         "regressor_kernels": table(prof["regressor"]),
         "note": "split_ms entries nest: support_threshold and proposal_sampling contain npe_sample / classifier_fit / "
                 "classifier_predict; simulate contains proposal_sampling and the simulator; per_round_ms[r] runs from "
-                "round r's simulate() to the next; the kernel tables come from a separate profiled run",
+                "round r's simulate() to the next; the kernel tables come from a separate profiled run (--full)",
     }
+    if args.dump_outputs:  # the last timed run's posterior: the simulations its rounds accepted
+        dump_outputs(args.dump_outputs, {"theta_train": post._theta_train, "x_train": post._x_train})
     print(json.dumps(line), flush=True)
 
 
@@ -757,69 +799,66 @@ def main():
     eng.prof_enable(args.profile_all)
     elapsed, out, step_s = timed(args.steps)   # headline: no per-launch events, fits overlapped
     assert torch.isfinite(out).all(), "non-finite posterior samples"
-    eng.prof_read()                            # drop anything recorded so far
-    eng.item_attn_fallback(reset=True)
-    eng.prof_enable(True)
-    prof_steps = max(1, min(args.prof_steps, args.steps))
-    if world > 1:
-        from npe_pfn.distributed import phase_timing
+    if args.dump_outputs and rank == 0:        # every rank holds the whole result; one writes it
+        dump_outputs(args.dump_outputs, {"samples": out})
+    prof = per_rank = alt_modes = None
+    if args.full:
+        eng.prof_read()                            # drop anything recorded so far
+        eng.item_attn_fallback(reset=True)
+        eng.prof_enable(True)
+        prof_steps = max(1, min(args.prof_steps, args.steps))
+        if world > 1:
+            from npe_pfn.distributed import collective_stats, phase_timing
 
-        phase_timing(True)
-    if world > 1:
-        from npe_pfn.distributed import collective_stats
+            phase_timing(True)
+            collective_stats(reset=True)           # count the profiled pass's collectives only
+        elapsed_prof, _, _ = timed(prof_steps)     # roofline / kernel table pass (fits in order)
+        eng.prof_enable(False)
+        prof = eng.prof_read()
+        ia_fb = eng.item_attn_fallback(reset=True)
+        if args.ia_stress != 1.0:
+            eng.debug_item_attn_scale(1.0)
+        if world > 1:
+            per_rank =per_rank_split(prof, prof_steps, elapsed_prof, rank, world)
+            coll = collective_stats()
+            per_rank["collective_bytes_per_step"] = {k: {"calls": v["calls"] / prof_steps, "bytes": v["bytes"] / prof_steps}
+                                                     for k, v in coll.items()}
+            per_rank["identity"] = rank_identity(dev, world, torch.distributed.get_backend())
+        if world > 1 and mode == "ep":
+            # the north_star form beside the default EP line (BASELINE.json north_star: replicated fit,
+            # row shards, ONE gather at the end): the same call with --mode rows, timed the same way
+            # in the same processes, its collectives counted, its draws compared with the EP call's
+            def step_rows():
+                return sample_rows_sharded(post, x_o, (N,))
 
-        collective_stats(reset=True)           # count the profiled pass's collectives only
-    elapsed_prof, _, _ = timed(prof_steps)     # roofline / kernel table pass (fits in order)
-    eng.prof_enable(False)
-    prof = eng.prof_read()
-    ia_fb = eng.item_attn_fallback(reset=True)
-    if args.ia_stress != 1.0:
+            for _ in range(max(1, args.warmup)):
+                step_rows()
+            collective_stats(reset=True)
+            _, _, rows_s = timed(args.steps, step_rows)
+            coll_rows = collective_stats()
+            rows_med = statistics.median(rows_s)
+            # one more call of each form from the same Philox counter: the draws must be equal
+            reg = post._model
+            c0 = reg.sample_counter
+            out_ep = step()
+            reg.sample_counter = c0
+            out_rows = step_rows()
+            alt_modes = {"rows": {
+                "value": round(N / rows_med, 2), "ms_per_step": round(rows_med * 1e3, 3),
+                "parallelism": f"rows{world} (row shards, replicated fit, one all_gather at the end)",
+                "step_ms": [round(v * 1e3, 3) for v in rows_s],
+                "collective_bytes_per_step": {k: {"calls": v["calls"] / args.steps, "bytes": v["bytes"] / args.steps}
+                                              for k, v in coll_rows.items()},
+                "draws_equal_to_ep": bool(torch.equal(out_rows, out_ep)),
+            }}
+    elif args.ia_stress != 1.0:
         eng.debug_item_attn_scale(1.0)
-    per_rank = None
-    if world > 1:
-        per_rank = per_rank_split(prof, prof_steps, elapsed_prof, rank, world)
-        from npe_pfn.distributed import collective_stats
-
-        coll = collective_stats()
-        per_rank["collective_bytes_per_step"] = {k: {"calls": v["calls"] / prof_steps, "bytes": v["bytes"] / prof_steps}
-                                                 for k, v in coll.items()}
-        per_rank["identity"] = rank_identity(dev, world, torch.distributed.get_backend())
-    alt_modes = None
-    if world > 1 and mode == "ep":
-        # the north_star form beside the default EP line (BASELINE.json north_star: replicated fit,
-        # row shards, ONE gather at the end): the same call with --mode rows, timed the same way
-        # in the same processes, its collectives counted, its draws compared with the EP call's
-        from npe_pfn.distributed import collective_stats
-
-        def step_rows():
-            return sample_rows_sharded(post, x_o, (N,))
-
-        for _ in range(max(1, args.warmup)):
-            step_rows()
-        collective_stats(reset=True)
-        _, _, rows_s = timed(args.steps, step_rows)
-        coll_rows = collective_stats()
-        rows_med = statistics.median(rows_s)
-        # one more call of each form from the same Philox counter: the draws must be equal
-        reg = post._model
-        c0 = reg.sample_counter
-        out_ep = step()
-        reg.sample_counter = c0
-        out_rows = step_rows()
-        alt_modes = {"rows": {
-            "value": round(N / rows_med, 2), "ms_per_step": round(rows_med * 1e3, 3),
-            "parallelism": f"rows{world} (row shards, replicated fit, one all_gather at the end)",
-            "step_ms": [round(v * 1e3, 3) for v in rows_s],
-            "collective_bytes_per_step": {k: {"calls": v["calls"] / args.steps, "bytes": v["bytes"] / args.steps}
-                                          for k, v in coll_rows.items()},
-            "draws_equal_to_ep": bool(torch.equal(out_rows, out_ep)),
-        }}
     # headline: the median timed call (SURVEY.md §8d / BASELINE.md: "the median of 5 runs"; with
     # the default --steps the median of >= 5); the mean over the K calls is reported beside it
     med_s = statistics.median(step_s)
     value = units / med_s
     traffic = None
-    if os.path.exists(args.traffic_json):
+    if args.full and os.path.exists(args.traffic_json):
         with open(args.traffic_json) as f:
             traffic = json.load(f)
     if args.config == "c2":
@@ -861,38 +900,39 @@ def main():
                        "available offline)",
         "config": {"workload": workload, "global_batch": units, "seq_len": n_sims, "parallelism": par,
                    "preprocessing": args.preprocessing},
-        "roofline": roofline(prof, traffic),
+        "roofline": roofline(prof, traffic) if args.full else None,
         "timing": {"statistic": f"median of the {args.steps} timed calls (each bracketed by barrier + synchronize)",
                    "value_mean": round(units * args.steps / elapsed, 2),
                    "ms_per_step_mean": round(elapsed / args.steps * 1e3, 3),
                    "step_ms": [round(v * 1e3, 3) for v in step_s], "region_s": round(elapsed, 4)},
     }
-    line["step_roofline"] = {
-        "algorithmic_tflop_per_step": round(sum(e["flops"] for e in prof) / prof_steps / 1e12, 3),
-        "achieved_tflops": round(sum(e["flops"] for e in prof) / elapsed_prof / 1e12, 2),
-        "kernel_time_frac": round(sum(e["ms"] for e in prof) / 1e3 / elapsed_prof, 3),
-        "ms_per_step_profiled": round(elapsed_prof / prof_steps * 1e3, 3),
-        "profiled_steps": prof_steps,
-        "rank": rank,
-    }
-    if per_rank is not None:
-        line["per_rank"] = per_rank
-    if alt_modes is not None:
-        line["alt_modes"] = alt_modes
-    line["kernels"] = {e["name"]: {"ms_per_step": round(e["ms"] / prof_steps, 2), "launches": e["launches"],
-                                   "tflops": round(e["flops"] / (e["ms"] / 1e3) / 1e12, 1) if e["flops"] else None,
-                                   "gbs": round(e["bytes"] / (e["ms"] / 1e3) / 1e9, 1)}
-                       for e in sorted(prof, key=lambda e: -e["ms"])}
-    if "k_item_attn" in line["kernels"]:
-        # share of query rows / blocks whose reference-free first pass failed its range check and
-        # took the online-softmax pass (device counters over the profiled pass)
-        line["kernels"]["k_item_attn"]["fallback_frac"] = round(ia_fb["fallback_frac"], 6)
-        line["kernels"]["k_item_attn"]["block_fallback_frac"] = round(ia_fb["block_fallback_frac"], 6)
+    if args.full:
+        line["step_roofline"] = {
+            "algorithmic_tflop_per_step": round(sum(e["flops"] for e in prof) / prof_steps / 1e12, 3),
+            "achieved_tflops": round(sum(e["flops"] for e in prof) / elapsed_prof / 1e12, 2),
+            "kernel_time_frac": round(sum(e["ms"] for e in prof) / 1e3 / elapsed_prof, 3),
+            "ms_per_step_profiled": round(elapsed_prof / prof_steps * 1e3, 3),
+            "profiled_steps": prof_steps,
+            "rank": rank,
+        }
+        if per_rank is not None:
+            line["per_rank"] = per_rank
+        if alt_modes is not None:
+            line["alt_modes"] = alt_modes
+        line["kernels"] = {e["name"]: {"ms_per_step": round(e["ms"] / prof_steps, 2), "launches": e["launches"],
+                                       "tflops": round(e["flops"] / (e["ms"] / 1e3) / 1e12, 1) if e["flops"] else None,
+                                       "gbs": round(e["bytes"] / (e["ms"] / 1e3) / 1e9, 1)}
+                           for e in sorted(prof, key=lambda e: -e["ms"])}
+        if "k_item_attn" in line["kernels"]:
+            # share of query rows / blocks whose reference-free first pass failed its range check and
+            # took the online-softmax pass (device counters over the profiled pass)
+            line["kernels"]["k_item_attn"]["fallback_frac"] = round(ia_fb["fallback_frac"], 6)
+            line["kernels"]["k_item_attn"]["block_fallback_frac"] = round(ia_fb["block_fallback_frac"], 6)
     if args.ia_stress != 1.0:
         line["config"]["ia_stress"] = args.ia_stress
         line["data"] += (f"; STRESS RUN: every item-attention score x{args.ia_stress} (fallback cost measurement, "
                          "not the model)")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == "c2":
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and args.config == "c2":
         line["cpu_baseline"] = cpu_baseline(theta_c, x_c, xo_c, N, args.cpu_rows, args.preprocessing,
                                             args.cpu_measured)
     elif rank == 0:

@@ -1,6 +1,7 @@
 """Wall-clock A/B of engine builds on one GPU: alternating `bench.py` subprocesses
 (NPFN_LIB=<lib>, no CPU baseline), median samples/s per library, and with NPFN_AB_KERNELS=1 the
-median per-call time of the main kernels from a 2-step profiled pass of the same process.
+median per-call time of the main kernels from a 2-step profiled pass (bench.py --full) of the same
+process.
 
 usage: python tools/ab_bench.py rounds libA.so libB.so [-- extra bench.py args]
 An arm may carry environment settings: lib.so@VAR=1,VAR2=x (same library, different switches).
@@ -27,8 +28,8 @@ for r in range(rounds):
         path, _, sets = lib.partition("@")
         env = dict(os.environ, NPFN_LIB=os.path.abspath(path))
         env.update(kv.split("=", 1) for kv in sets.split(",") if kv)
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--no-cpu-baseline",
-               "--prof-steps", "2" if with_k else "0"] + extra
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--no-cpu-baseline"]
+        cmd += (["--full", "--prof-steps", "2"] if with_k else []) + extra
         out = subprocess.run(cmd, env=env, check=True, timeout=400, capture_output=True, text=True).stdout
         line = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
         res[lib].append(line["value"])
