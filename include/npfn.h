@@ -225,6 +225,37 @@ int npfn_sir_select(const float* lpr, const float* lq, const float* thr, int64_t
                     uint64_t seed, uint64_t counter, int64_t group_offset, const float* theta,
                     int32_t dim, int64_t* pick_out, float* ess_out, float* theta_out, void* stream);
 
+/* K13: seeded k-means (Lloyd) of pts [n_rows, dim] into k clusters.  centers [k, dim] float32,
+ * labels [n_rows] int64, counts [k] int64, n_iter [1] int64 -- all DEVICE.  Deterministic:
+ * the same inputs and seed give the same bits on every run.
+ * The algorithm (TabPFN_Based_Uncond_Estimator's clustering, reference npe_pfn.py:793-794;
+ * all distances and sums in fp64 on the fp32 points):
+ *  - tol_abs = tol * mean_j(population variance of column j) (sklearn's scaling of tol);
+ *  - k-means++ seeding, one candidate per centre, u_c = Philox4x32-10(counter = (c, 0),
+ *    key = seed): centre 0 = row min(floor(u_0 n), n - 1); centre c = the first row whose
+ *    inclusive prefix sum of d2 (squared distance to the nearest chosen centre) exceeds
+ *    u_c * sum(d2) (the last row with d2 > 0 if rounding puts the target past the total;
+ *    row min(floor(u_c n), n - 1) if sum(d2) == 0);
+ *  - Lloyd: labels = nearest centre (ties: lower index), centre = fp64 mean of its members
+ *    (an empty cluster keeps its centre), shift = sum_c |new_c - old_c|^2; stops after the
+ *    iteration with shift <= tol_abs or at max_iter; n_iter = iterations run;
+ *  - the centres are rounded to fp32 and stored; labels and counts are computed against the
+ *    stored centres, so npfn_kmeans_assign(pts, centers) returns labels bit for bit.
+ * Iterations past convergence are no-ops on the device; the host reads the device's
+ * convergence flag every 8 iterations, and for that read alone this call WAITS on the stream
+ * (so it cannot be captured into a graph); it returns with the final assignment queued.
+ * Errors: NPFN_EINVAL for k < 1, k > n_rows, dim < 1, k * dim > 4096 (the centres are held
+ * in LDS as fp64, 32 KB) or n_rows >= 2^31; NPFN_ENOMEM when the workspace (8 n_rows bytes +
+ * at most 16 MB of partial sums) does not fit; NPFN_EHIP for a launch error. */
+int npfn_kmeans_fit(const float* pts, int64_t n_rows, int32_t dim, int32_t k, uint64_t seed,
+                    int32_t max_iter, float tol, float* centers, int64_t* labels, int64_t* counts,
+                    int64_t* n_iter, void* stream);
+/* K13 predict: labels[i] = argmin_c ||pts[i] - centers[c]||^2 (ties: lower c), fp64 distances
+ * of the fp32 inputs (KMeans.predict, reference npe_pfn.py:855).  Asynchronous.  Same caps on
+ * dim, k * dim and n_rows as npfn_kmeans_fit. */
+int npfn_kmeans_assign(const float* pts, int64_t n_rows, int32_t dim, const float* centers, int32_t k,
+                       int64_t* labels, void* stream);
+
 /* Estimator-parallel split (npe_pfn/distributed.py): from the next fit on,
  * fits and forwards compute only estimators [e0, e0 + count) of cfg.n_estimators (the
  * feature permutation and preprocessing of estimator e are the same as in the full

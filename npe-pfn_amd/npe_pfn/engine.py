@@ -95,6 +95,8 @@ SIGNATURES = {
     "npfn_compact_rows": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     "npfn_filter_stdeuclid": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i64, _vp, _vp]),
     "npfn_sir_select": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _u64, _u64, _i64, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "npfn_kmeans_fit": (ctypes.c_int, [_vp, _i64, _i32, _i32, _u64, _i32, _f, _vp, _vp, _vp, _vp, _vp]),
+    "npfn_kmeans_assign": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp]),
     "npfn_set_estimator_range": (ctypes.c_int, [_vp, _i32, _i32]),
     "npfn_set_estimator_set": (ctypes.c_int, [_vp, _i32, _i32, _i32]),
     "npfn_forward_targets": (ctypes.c_int, [_vp, _vp, _i64, _i64, _vp, _vp]),
@@ -426,6 +428,37 @@ class Engine:
         _check(self.lib, self.lib.npfn_filter_stdeuclid(_ptr(x), x.shape[0], x.shape[1], _ptr(obs), int(k), _ptr(idx),
                                                         self.stream), "npfn_filter_stdeuclid")
         return idx
+
+    def kmeans_fit(self, theta: torch.Tensor, k: int, seed: int, max_iter: int = 300,
+                   tol: float = 1e-4) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """K13 (npfn_kmeans_fit): seeded k-means of theta [n, dim] -> (centers [k, dim] float32,
+        labels [n] int64, counts [k] int64, n_iter [1] int64), all on the device."""
+        theta = _dev_f32(theta, self.device)
+        if theta.ndim != 2:
+            raise ValueError(f"kmeans_fit: theta must be [n, dim], got {tuple(theta.shape)}")
+        n, dim = theta.shape
+        k = int(k)
+        centers = torch.empty((max(k, 0), dim), dtype=torch.float32, device=self.device)
+        labels = torch.empty(n, dtype=torch.int64, device=self.device)
+        counts = torch.empty(max(k, 0), dtype=torch.int64, device=self.device)
+        n_iter = torch.empty(1, dtype=torch.int64, device=self.device)
+        _check(self.lib, self.lib.npfn_kmeans_fit(_ptr(theta), n, dim, k, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                  int(max_iter), float(tol), _ptr(centers), _ptr(labels),
+                                                  _ptr(counts), _ptr(n_iter), self.stream), "npfn_kmeans_fit")
+        return centers, labels, counts, n_iter
+
+    def kmeans_assign(self, theta: torch.Tensor, centers: torch.Tensor) -> torch.Tensor:
+        """K13 predict (npfn_kmeans_assign): index of the nearest of centers [k, dim] per row of theta."""
+        theta = _dev_f32(theta, self.device)
+        centers = _dev_f32(centers, self.device)
+        if theta.ndim != 2 or centers.ndim != 2 or theta.shape[1] != centers.shape[1]:
+            raise ValueError(f"kmeans_assign: theta {tuple(theta.shape)} and centers {tuple(centers.shape)} "
+                             "do not match")
+        labels = torch.empty(theta.shape[0], dtype=torch.int64, device=self.device)
+        _check(self.lib, self.lib.npfn_kmeans_assign(_ptr(theta), theta.shape[0], theta.shape[1], _ptr(centers),
+                                                     centers.shape[0], _ptr(labels), self.stream),
+               "npfn_kmeans_assign")
+        return labels
 
     # ------------------------------------------------- estimator-parallel split
     def set_estimator_range(self, e0: int, count: int) -> None:

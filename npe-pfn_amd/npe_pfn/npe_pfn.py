@@ -1,7 +1,7 @@
 """NPE-PFN estimators (reference: npe_pfn/npe_pfn.py).
 
-Public surface kept from the reference: ``NPE_PFN_Core`` (:26-600) and
-``TabPFN_Based_NPE_PFN`` (:708-744) with ``append_simulations``, ``sample``,
+Public surface kept from the reference: ``NPE_PFN_Core`` (:26-600),
+``TabPFN_Based_NPE_PFN`` (:708-744) and ``TabPFN_Based_Uncond_Estimator`` (:747-900) with ``append_simulations``, ``sample``,
 ``sample_batched``, ``log_prob`` and pickling.  The autoregressive loop
 (``_sample`` :111-169, ``_sample_batched`` :171-251,
 ``_autoregressive_log_prob`` :462-524) has two implementations:
@@ -23,11 +23,13 @@ import contextlib
 import math
 from typing import Callable, Mapping, Optional, Tuple, Union
 
+import numpy as np
 import torch
 from torch import Tensor
 from torch.distributions import Distribution
 
 from .accept_reject_sampler import accept_reject_sample
+from .kmeans import KMeansState
 from .support_posterior import (get_filtering_method, latest_filtering, no_filtering,
                                 standardized_euclidean_filtering)
 from .tabpfn import TabPFNClassifier, TabPFNRegressor
@@ -495,3 +497,121 @@ class TabPFN_Based_NPE_PFN(NPE_PFN_Core):
     def get_context(self, x: Tensor) -> Tuple[Tensor, Tensor]:
         x = self._validate_x(x)
         return self.filter(x, self._theta_train, self._x_train, self.filter_context_size)
+
+
+class TabPFN_Based_Uncond_Estimator(NPE_PFN_Core):
+    """Unconditional density estimator of theta (reference :747-900, "experimental" there).
+
+    The thetas are clustered by k-means (``num_clusters=1``: no clustering) and each cluster is
+    modelled by the autoregressive TabPFN sampler on a dummy one-column x ~ N(0, 1); the mixture
+    weights are the cluster sizes.  The clustering is the seeded k-means of :mod:`npe_pfn.kmeans`
+    (K13: on the device with the engine-backed regressor, in numpy with any other estimator)
+    instead of the reference's host-side sklearn ``KMeans``; its seed is
+    ``regressor_init_kwargs["random_state"]``.  Every host draw (``randperm``, ``randn``,
+    ``multinomial``) comes from the CPU generators in the reference's order, so one
+    ``torch.manual_seed`` / ``np.random.seed`` gives the same stream with every estimator.
+    """
+
+    def __init__(
+        self,
+        num_clusters: int = 1,
+        show_progress_bars: bool = False,
+        regressor_init_kwargs: Mapping = {},
+        classifier_init_kwargs: Mapping = {},
+    ):
+        super().__init__(show_progress_bars, prior=None, regressor_init_kwargs=regressor_init_kwargs,
+                         classifier_init_kwargs=classifier_init_kwargs)
+        self.context_size = 10_000  # rows of a cluster beyond this are cut off (reference :764-765)
+        self.num_clusters = num_clusters
+        self.cluster_state = 0
+        self.kmeans: Optional[KMeansState] = None
+        self.counts = None
+
+    def set_cluster_state(self, cluster_idx: int = 0):
+        self.cluster_state = cluster_idx
+
+    def _kmeans_engine(self):
+        """The engine that clusters on the device; None with a generic estimator (host k-means)."""
+        return self._model.engine if self._fused() else None
+
+    def get_context(self, x: Tensor) -> Tuple[Tensor, Tensor]:
+        """The current cluster's first ``context_size`` rows (reference :774-781)."""
+        member = self.kmeans.labels_ == self.cluster_state
+        return self._theta_train[member][: self.context_size], self._x_train[member][: self.context_size]
+
+    def append_simulations(self, theta: Tensor, x: Tensor = None):
+        """Replace the training thetas (``x`` is ignored) and cluster them (reference :783-800)."""
+        self._theta_train = None
+        self._x_train = None
+        theta = self._validate_theta(theta)
+        if not bool(torch.isfinite(theta).all()):
+            raise ValueError("append_simulations: theta has non-finite entries (k-means needs finite thetas)")
+        n = theta.shape[0]
+        # permuted because only the first context_size rows of a cluster reach the context
+        self._theta_train = theta[torch.randperm(n).to(theta.device)]
+        self._x_train = torch.randn(n, 1).to(theta.device)
+        seed = self.regressor_init_kwargs.get("random_state", 0)
+        self.kmeans = KMeansState(self.num_clusters, seed=0 if seed is None else int(seed))
+        self.kmeans.fit(self._theta_train, engine=self._kmeans_engine())
+        counts = self.kmeans.counts.numpy()
+        assert counts.min() > 1, "Too few samples in some clusters, need at least 2."
+        self.counts = counts
+        return self
+
+    def sample(self, sample_shape: torch.Size = torch.Size(), x: Tensor = None, max_sampling_batch_size: int = 10_000,
+               with_log_prob: bool = False, eps: float = 1e-15) -> Union[Tensor, Tuple[Tensor, Tensor]]:
+        """``sample_shape[0]`` draws of the mixture (reference :802-844); ``x`` is ignored.
+
+        No fit token: the engine keeps one set of cached fits, and every cluster has its own context."""
+        per_cluster = np.random.multinomial(sample_shape[0], self.counts / self.counts.sum())
+        draws, lps = [], []
+        for c, m in enumerate(per_cluster):
+            self.set_cluster_state(c)
+            if m == 0:
+                continue
+            th, lp = self._sample(max_sampling_batch_size, torch.randn(int(m), 1), repeat_x=False,
+                                  with_log_prob=with_log_prob, eps=eps)
+            draws.append(th)
+            lps.append(lp)
+        self.set_cluster_state()
+        out_device = self._theta_train.device
+        samples = torch.cat(draws, dim=0)
+        perm = torch.randperm(samples.shape[0])
+        samples = samples[perm.to(samples.device)].to(out_device)
+        if with_log_prob:
+            log_probs = torch.cat(lps, dim=0)
+            return samples, log_probs[perm.to(log_probs.device)].to(out_device)
+        return samples
+
+    def log_prob(self, theta: Tensor, x: Tensor = None, max_sampling_batch_size: int = 10_000,
+                 mode: str = "autoregressive", eps: float = 1e-15, **ratio_kwargs) -> Tensor:
+        """log of the mixture's component density at theta's own cluster plus the log cluster
+        weight (reference :846-900); ``x`` is ignored.  Every cluster visit takes a fresh fit
+        token around its chunks: a token kept across clusters would let two clusters of equal
+        size reuse each other's fits."""
+        if mode == "ratio_based":
+            raise NotImplementedError(
+                "TabPFN_Based_Uncond_Estimator.log_prob: mode='ratio_based' is not provided (the reference's "
+                "version draws from the whole mixture inside the per-cluster loop and adds the cluster weight "
+                "twice); use mode='autoregressive'")
+        if mode != "autoregressive":
+            raise ValueError(f"Invalid mode: {mode}")
+        theta = self._validate_theta(theta)
+        labels = self.kmeans.predict(theta, engine=self._kmeans_engine())
+        log_weights = np.log(self.counts / self.counts.sum())
+        out = torch.zeros(theta.shape[0])
+        for c in range(self.num_clusters):
+            self.set_cluster_state(c)
+            rows = (labels == c).nonzero(as_tuple=True)[0]
+            if rows.numel() == 0:
+                continue
+            members = theta[rows]
+            lp = torch.zeros(members.shape[0])
+            with self._reuse_fits():
+                for i in range(0, members.shape[0], max_sampling_batch_size):
+                    chunk = members[i: i + max_sampling_batch_size]
+                    lp[i: i + max_sampling_batch_size] = self._autoregressive_log_prob(
+                        chunk, torch.randn(chunk.shape[0], 1), repeat_x=False, eps=eps).cpu()
+            out[rows.cpu()] = lp + float(log_weights[c])
+        self.set_cluster_state()
+        return out
