@@ -154,6 +154,44 @@ int npfn_bar_sample(const float* logits, const float* borders, int64_t n_rows, i
 int npfn_bar_nll(const float* logits, const float* borders, const float* y, int64_t n_rows,
                  int32_t n_bars, float* out, void* stream);
 
+/* criterion.mean(logits), .median(logits), .mode(logits) and .icdf(logits, q) [ext: tabpfn 2.2.1
+ * FullSupportBarDistribution] of each row of logits [n_rows, n_bars] in one pass.  With borders
+ * b[0..n_bars], widths w_j = b[j+1] - b[j], p = softmax(logits row), HM = the half-normal median
+ * 0.6744897501960817:
+ *  - mean_out [n_rows] = sum_j p_j m_j, m_j = b[j] + w_j / 2 for the inner bars and the
+ *    half-normal means m_0 = b[1] - (w_0 / HM) sqrt(2 / pi), m_last = b[n_bars-1] +
+ *    (w_last / HM) sqrt(2 / pi) for the two tail bars (the scales of the NLL); summed in fp64;
+ *  - quant_out [n_q][n_rows] (quantile i contiguous) = icdf(quantiles[i]): the arithmetic of
+ *    npfn_bar_sample with u = q -- the first bar with mass whose cumulative sum reaches q * total,
+ *    linear interpolation inside it (tail bars included) with the fraction clamped to [0, 1], the
+ *    last bar with mass if q lies beyond the rounded total; above q = 1 - 2^-8, where fp32 sums
+ *    from the left no longer resolve the tail, the same search on the complement summed from the
+ *    right (the first bar with mass that leaves at most 1 - q to its right); q = 0 / 1 give the
+ *    left / right border of the first / last bar with mass, never a point inside a zero-mass
+ *    bar; q outside [0, 1] is clamped; the median is q = 0.5;
+ *  - mode_out [n_rows] = the centre b[j] + w_j / 2 of the bar with the largest p_j / w_j (the
+ *    lowest j on ties, tail bars with the plain centre, bars with w_j == 0 skipped).
+ * quantiles is a DEVICE array of n_q <= 64 levels.  Any output may be NULL (that statistic is
+ * skipped); n_q == 0 allows quantiles and quant_out to be NULL.  A row without a finite logit
+ * gives NaN.  Asynchronous; n_rows == 0 launches nothing.
+ * Errors: NPFN_EINVAL for n_bars < 2, n_q < 0, n_q > 64 or a missing pointer. */
+int npfn_bar_stats(const float* logits, const float* borders, int64_t n_rows, int32_t n_bars,
+                   const float* quantiles, int32_t n_q, float* mean_out, float* mode_out,
+                   float* quant_out, void* stream);
+
+/* predict(X, output_type="mean" | "median" | "mode" | "quantiles" | "main", quantiles=...) [ext:
+ * tabpfn 2.2.1 TabPFNRegressor.predict]: npfn_predict's forward and ensemble mix, then the
+ * summaries of npfn_bar_stats on the last fit's borders -- 8192 query rows at a time through an
+ * engine-owned window of mixture logits (164 MB at 5000 bars);
+ * the [n_rows, n_bars] fp32 logits of npfn_predict are never allocated.
+ * Outputs, NULL outputs, the quantile list and n_q as for npfn_bar_stats.  Asynchronous;
+ * honours npfn_set_average_before_softmax.
+ * Errors: NPFN_EINVAL as for npfn_bar_stats and for ldq < n_features; NPFN_ESTATE before a fit,
+ * after a classifier fit, or on a partial estimator range. */
+int npfn_predict_stats(npfn_engine* h, const float* Xq, int64_t ldq, int64_t n_rows,
+                       const float* quantiles, int32_t n_q, float* mean_out, float* mode_out,
+                       float* quant_out, void* stream);
+
 /* Fused autoregressive sampler: the whole `for param_idx in range(dim_theta)`
  * loop of NPE_PFN_Core._sample / _sample_batched (npe_pfn.py:135-169,
  * 211-241) on the device.  x_ctx [n_ctx, dim_x], theta_ctx [n_ctx, dim_theta]

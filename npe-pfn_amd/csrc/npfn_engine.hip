@@ -69,12 +69,13 @@ struct LayerW {
 enum ProfCat {
   P_ENCODE, P_GEMM_BF16, P_GEMM_GELU, P_GEMM_F32, P_GEMM_LN, P_FEAT_ATTN, P_KV_PACK, P_ITEM_ATTN,
   P_MIX_SAMPLE, P_MIX_NLL, P_MIX_LOG, P_STATS, P_ROW_LAYER, P_CLS_MIX, P_VIEWS, P_QUANT_FIT, P_POWER_FIT,
-  P_SVD_FIT, P_FP_TRAIN, P_TARGET_TF, P_OTHER, P_NCAT
+  P_SVD_FIT, P_FP_TRAIN, P_TARGET_TF, P_BAR_STATS, P_OTHER, P_NCAT
 };
 const char* kProfNames[P_NCAT] = {
   "k_encode", "k_gemm<EPI_BF16>", "k_gemm<EPI_BF16_GELU>", "k_gemm<EPI_LOGIT>", "k_gemm<EPI_LN>", "k_feat_attn",
   "k_kv_pack", "k_item_attn", "k_mix_sample", "k_mix_nll", "k_mix_log", "k_col_stats+k_build_params", "k_row_layer",
-  "k_cls_mix", "k_views", "k_quantile_fit", "k_power_fit", "k_svd_fit", "k_fp_train", "k_target_tf", "other"};
+  "k_cls_mix", "k_views", "k_quantile_fit", "k_power_fit", "k_svd_fit", "k_fp_train", "k_target_tf", "k_bar_stats",
+  "other"};
 
 struct ProfRec {
   int cat;  // + P_NCAT: launched on a side stream (the AR fits' preprocessing / train forwards)
@@ -180,6 +181,7 @@ struct npfn_engine {
   DevBuf dh, logits, tgt;
   DevBuf joint, feat, logp;
   DevBuf pu;  // [n_unique][nb] step-0 mixtures of npfn_ar_sample_repeated
+  DevBuf mixlog, borders;  // npfn_predict_stats: [kStatsRows][nb] mixture logits of a row window, [nb + 1] borders
   int64_t chunk_rows = 16384;
   // estimator set of fits and forwards (npfn_set_estimator_set): estimators e0 + es * i,
   // i < ne, of cfg.n_estimators; a partial set is the estimator-parallel multi-GPU split
@@ -1474,7 +1476,7 @@ int npfn_engine_destroy(npfn_engine* h) {
   h->wmain.release();
   h->wside.release();
   DevBuf* bufs[] = {&h->dh,      &h->logits, &h->tgt,
-                    &h->joint, &h->feat,     &h->logp, &h->pu, &h->views, &h->ftype, &h->ett,     &h->fp_salt};
+                    &h->joint, &h->feat,     &h->logp, &h->pu, &h->mixlog, &h->borders, &h->views, &h->ftype, &h->ett,     &h->fp_salt};
   for (DevBuf* b : bufs) free_buf(*b);
   delete h;
   return NPFN_OK;
@@ -1549,6 +1551,60 @@ int npfn_predict(npfn_engine* h, const float* Xq, int64_t ldq, int64_t n_rows, f
     ProfGuard g(h, P_MIX_LOG, 0.0, (double)E * rows * nb * sizeof(logit_t) + (double)rows * nb * 4, s);
     launch_mix_log((const logit_t*)h->logits.p, rows, E, nb, invT, h->mixtrans(), logits + r0 * nb, nb, s);
   }
+  HIPCHK(hipGetLastError());
+  return NPFN_OK;
+}
+
+constexpr int64_t kStatsRows = 8192;  // rows of mixture logits between k_mix_log and k_bar_stats
+
+int npfn_predict_stats(npfn_engine* h, const float* Xq, int64_t ldq, int64_t n_rows, const float* quantiles,
+                       int32_t n_q, float* mean_out, float* mode_out, float* quant_out, void* stream) {
+  RCHK(check_engine(h));
+  if (!h->f->fitted) return fail(NPFN_ESTATE, "predict_stats before fit");
+  if (h->f->ncls > 0) return fail(NPFN_ESTATE, "predict_stats (bar summaries) after a classifier fit; use predict_proba");
+  RCHK(need_full_range(h, "predict_stats"));
+  if (n_q < 0 || n_q > 64) return fail(NPFN_EINVAL, "predict_stats: n_q must be in [0, 64]");
+  if (n_rows == 0) return NPFN_OK;
+  if (!Xq || (n_q > 0 && (!quantiles || !quant_out))) return fail(NPFN_EINVAL, "predict_stats: null pointer");
+  if (ldq < h->f->F) return fail(NPFN_EINVAL, "predict_stats: ldq < n_features");
+  hipStream_t s = (hipStream_t)stream;
+  const int E = h->cfg.n_estimators, nb = h->cfg.n_bars;
+  const float invT = 1.0f / h->cfg.softmax_temperature;
+  const int n_out = (mean_out ? 1 : 0) + (mode_out ? 1 : 0) + n_q;
+  // the mixture's fp32 logits of kStatsRows rows at a time (164 MB at 5000 bars: written and read
+  // back through the cache), never those of the whole call
+  RCHK(ensure(h->mixlog, (size_t)std::min<int64_t>(kStatsRows, n_rows) * nb * sizeof(float), s));
+  RCHK(ensure(h->borders, (size_t)(nb + 1) * sizeof(float), s));
+  launch_borders(h->bz, (const float*)h->f->ystats.p, nb, (float*)h->borders.p, s);
+  for (int64_t r0 = 0; r0 < n_rows; r0 += h->chunk_rows) {
+    const int64_t rows = std::min(h->chunk_rows, n_rows - r0);
+    RCHK(predict_logits_chunk(h, Xq + r0 * ldq, ldq, rows, s));
+    for (int64_t r1 = 0; r1 < rows; r1 += kStatsRows) {
+      const int64_t sub = std::min<int64_t>(kStatsRows, rows - r1);
+      const int64_t o = r0 + r1;
+      {
+        ProfGuard g(h, P_MIX_LOG, 0.0, (double)E * sub * nb * sizeof(logit_t) + (double)sub * nb * 4, s);
+        launch_mix_log_rows((const logit_t*)h->logits.p, rows, r1, sub, E, nb, invT, h->mixtrans(), (float*)h->mixlog.p,
+                            nb, s);
+      }
+      ProfGuard g(h, P_BAR_STATS, 0.0, (double)sub * nb * 4 + (double)sub * n_out * 4, s);
+      launch_bar_stats((const float*)h->mixlog.p, (const float*)h->borders.p, sub, nb, quantiles, n_q,
+                       mean_out ? mean_out + o : nullptr, mode_out ? mode_out + o : nullptr,
+                       n_q > 0 ? quant_out + o : nullptr, n_rows, s);
+    }
+  }
+  HIPCHK(hipGetLastError());
+  return NPFN_OK;
+}
+
+int npfn_bar_stats(const float* logits, const float* borders, int64_t n_rows, int32_t n_bars, const float* quantiles,
+                   int32_t n_q, float* mean_out, float* mode_out, float* quant_out, void* stream) {
+  if (n_bars < 2 || n_q < 0 || n_q > 64) return fail(NPFN_EINVAL, "bar_stats: need n_bars >= 2 and n_q in [0, 64]");
+  if (n_rows == 0) return NPFN_OK;
+  if (!logits || !borders || (n_q > 0 && (!quantiles || !quant_out)))
+    return fail(NPFN_EINVAL, "bar_stats: null pointer");
+  launch_bar_stats(logits, borders, n_rows, n_bars, quantiles, n_q, mean_out, mode_out, n_q > 0 ? quant_out : nullptr,
+                   n_rows, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return NPFN_OK;
 }

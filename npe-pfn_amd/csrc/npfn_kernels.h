@@ -286,6 +286,13 @@ void launch_group_nll(const float* p_rows, int64_t per, int64_t R, int nb, const
 void launch_mix_nll(const logit_t* logits, int64_t R, int E, int nb, float invT, const MixTrans& tr, const float* bz,
                     const float* ystats, int64_t row_offset, const float* feat, int64_t ldf, int col,
                     float* logp_acc, float log_eps, hipStream_t s);
+// launch_mix_log over rows [row0, row0 + R) of logits [E][ld_rows][nb]; out row r = row row0 + r
+void launch_mix_log_rows(const logit_t* logits, int64_t ld_rows, int64_t row0, int64_t R, int E, int nb, float invT,
+                         const MixTrans& tr, float* out, int64_t ldo, hipStream_t s);
+// Mean / mode / quantiles of softmax(logits row) (bar_stats_row): q [n_q <= 64] DEVICE quantile
+// levels; row r writes mean_out / mode_out [r] and quant_out [i * ldq_out + r]; null outputs skipped
+void launch_bar_stats(const float* logits, const float* borders, int64_t R, int nb, const float* q, int n_q,
+                      float* mean_out, float* mode_out, float* quant_out, int64_t ldq_out, hipStream_t s);
 void launch_bar_sample(const float* logits, const float* borders, int64_t R, int nb, uint64_t seed,
                        uint64_t counter, float* out, hipStream_t s);
 void launch_bar_nll(const float* logits, const float* borders, const float* y, int64_t R, int nb, float* out,

@@ -2791,6 +2791,214 @@ __device__ void bar_sample_row(const float* __restrict__ p, const float* __restr
   }
 }
 
+// Summaries of one row's bar distribution (tabpfn's FullSupportBarDistribution.mean / .median /
+// .mode / .icdf [ext]) from probabilities p[0..nb) in LDS (unnormalized, divided by their sum),
+// borders bz * bscale + bshift:
+// * quantile i = icdf(q[i]): the arithmetic of bar_sample_row with u = q[i] -- the same contiguous
+//   per-thread segments, block scan and serial cumulative sums, so the bar found and the fraction
+//   inside it are those of a draw at that uniform (the result is additionally clamped into its
+//   bar).  The search of all quantiles shares one scan: every thread keeps its first / last bar
+//   with mass and their cumulative sums, so only the thread a quantile crosses in walks its bars
+//   again; the lowest bar per quantile comes from a DPP wave minimum and one LDS atomic per wave,
+//   and thread i finishes quantile i (its prefix recomputed from the owner's scan prefix, the
+//   same additions in the same order).  Above q = 1 - kStatsUpperTail the left-to-right fp32 sums
+//   cannot resolve the tail (they carry ~2^-23 of the total, the tail holds 1 - q of it): there
+//   thread i sums the complement from the right instead -- whole thread segments first, then
+//   bars -- and takes the first bar with mass that leaves at most (1 - q) total to its right,
+//   so q = 1 is exactly the right border of the last bar with mass.
+// * mean = sum_j p_j m_j / sum_j p_j in fp64 (no cancellation against a large |border|), m_j the
+//   bar centre, the half-normal means b[1] - s0 sqrt(2 / pi), b[nb - 1] + s1 sqrt(2 / pi) for the
+//   two tail bars (scales w / NPFN_HALFNORMAL_MEDIAN, as in the NLL).
+// * mode = centre of the bar with the largest p_j / w_j (lowest j on ties, w_j == 0 skipped).
+// A row whose total is not a positive finite number (no finite logit) gives NaN.  Every index
+// used comes from a bar inside [0, nb), whatever p holds.
+constexpr int kStatsMaxQ = 64;
+constexpr float kStatsUpperTail = 0.00390625f;   // 2^-8: 2^-23 / 2^-8 keeps ~1e-4 of the tail mass
+struct BarStatsWs {          // static LDS of k_bar_stats
+  float q[kStatsMaxQ];       // the quantile list, read from the device array once per block
+  int qidx[kStatsMaxQ];      // per quantile: the lowest bar found (0x7fffffff: none)
+  float excl[256];           // every thread's scan prefix,
+  float loc[256];            // segment sum
+  int first[256];            // and first bar with mass (-1: none)
+  float scan[4];
+  double msum[4], psum[4];
+  float dmax[4];
+  int dj[4];
+  int lastnz;
+};
+
+__device__ void bar_stats_row(const float* __restrict__ p, const float* __restrict__ bz, float bscale, float bshift,
+                              int nb, int n_q, BarStatsWs& ws, float* __restrict__ mean_out,
+                              float* __restrict__ mode_out, float* __restrict__ quant_out, int64_t ldq_out) {
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int per = (nb + 255) / 256;
+  const int b0 = min(tid * per, nb);
+  const int b1 = min(b0 + per, nb);
+  float local = 0.f;
+  for (int b = b0; b < b1; ++b) local += p[b];
+  float incl = wave_incl_scan_dpp(local);
+  if (lane == 63) ws.scan[w] = incl;
+  if (tid < n_q) ws.qidx[tid] = 0x7fffffff;
+  if (tid == 0) ws.lastnz = 0;
+  __syncthreads();
+  float base = 0.f, total = 0.f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const float t = ws.scan[k];
+    if (k < w) base += t;
+    total += t;
+  }
+  incl += base;
+  const float excl = incl - local;
+  ws.excl[tid] = excl;
+  ws.loc[tid] = local;
+  // the thread's first / last bar with mass and the serial cumulative sums after them
+  int first = -1, lastnz = -1;
+  float cn_first = 0.f, cn_last = 0.f;
+  {
+    float c = excl;
+    for (int b = b0; b < b1; ++b) {
+      const float cn = c + p[b];
+      if (p[b] > 0.f) {
+        if (first < 0) { first = b; cn_first = cn; }
+        lastnz = b;
+        cn_last = cn;
+      }
+      c = cn;
+    }
+  }
+  ws.first[tid] = first;
+  {
+    const float m = wave_max_dpp((float)lastnz);
+    if (lane == 0 && m >= 0.f) atomicMax(&ws.lastnz, (int)m);
+  }
+  for (int i = 0; i < n_q; ++i) {
+    const float u = fminf(fmaxf(ws.q[i], 0.f), 1.f);
+    if (1.0f - u < kStatsUpperTail) continue;   // summed from the right by thread i below
+    const float ut = u * total;
+    int found = -1;
+    if (first >= 0 && cn_last >= ut) {   // the sums never decrease: some bar with mass reaches ut
+      if (cn_first >= ut) {
+        found = first;
+      } else {
+        float c = excl;
+        for (int b = b0; b < b1; ++b) {
+          const float cn = c + p[b];
+          if (p[b] > 0.f && cn >= ut) { found = b; break; }
+          c = cn;
+        }
+      }
+    }
+    const float m = wave_max_dpp(found >= 0 ? -(float)found : -INFINITY);  // bar indices are exact in fp32
+    if (lane == 0 && m > -INFINITY) atomicMin(&ws.qidx[i], (int)(-m));
+  }
+  if (mean_out != nullptr || mode_out != nullptr) {
+    double msum = 0.0, psum = 0.0;
+    float dbest = -INFINITY;
+    int jbest = -1;
+    float left = b0 < b1 ? bz[b0] * bscale + bshift : 0.f;
+    for (int b = b0; b < b1; ++b) {
+      const float right = bz[b + 1] * bscale + bshift;
+      const float pb = p[b];
+      const double wd = (double)right - (double)left;
+      double m = 0.5 * ((double)left + (double)right);
+      if (b == 0) m = (double)right - wd / NPFN_HALFNORMAL_MEDIAN * 0.7978845608028654;   // sqrt(2 / pi)
+      if (b == nb - 1) m = (double)left + wd / NPFN_HALFNORMAL_MEDIAN * 0.7978845608028654;
+      msum += (double)pb * m;
+      psum += (double)pb;
+      const float wf = right - left;
+      if (wf > 0.f) {
+        const float d = pb / wf;
+        if (d > dbest) { dbest = d; jbest = b; }
+      }
+      left = right;
+    }
+    msum = wave_sum_d(msum);
+    psum = wave_sum_d(psum);
+    const float dm = wave_max_dpp(dbest);
+    const float jm = wave_max_dpp((jbest >= 0 && dbest == dm) ? -(float)jbest : -INFINITY);
+    if (lane == 0) {
+      ws.msum[w] = msum;
+      ws.psum[w] = psum;
+      ws.dmax[w] = dm;
+      ws.dj[w] = jm > -INFINITY ? (int)(-jm) : -1;
+    }
+  }
+  __syncthreads();
+  const bool valid = total > 0.f && total < INFINITY;
+  if (tid == 0) {
+    if (mean_out != nullptr) {
+      const double ms = (ws.msum[0] + ws.msum[1]) + (ws.msum[2] + ws.msum[3]);
+      const double ps = (ws.psum[0] + ws.psum[1]) + (ws.psum[2] + ws.psum[3]);
+      *mean_out = valid ? (float)(ms / ps) : NAN;
+    }
+    if (mode_out != nullptr) {
+      float dm = -INFINITY;
+      int j = -1;
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (ws.dj[k] >= 0 && ws.dmax[k] > dm) { dm = ws.dmax[k]; j = ws.dj[k]; }  // ties: the lower wave's bar
+      float md = NAN;
+      if (valid && j >= 0) {
+        const float left = bz[j] * bscale + bshift, right = bz[j + 1] * bscale + bshift;
+        md = left + 0.5f * (right - left);
+      }
+      *mode_out = md;
+    }
+  }
+  if (tid < n_q) {
+    const float u = fminf(fmaxf(ws.q[tid], 0.f), 1.f);
+    const float v = 1.0f - u;   // exact for u >= 0.5
+    int idx;
+    float frac;
+    if (v < kStatsUpperTail) {
+      // S = the mass right of the current position; a bar is a candidate while S <= v total
+      const float vt = v * total;
+      int cand = -1, tj = 0;
+      float cand_s = 0.f, sj = 0.f, S = 0.f;
+      bool whole = false;   // cand is the first bar with mass of a segment taken whole
+      for (int t = (nb - 1) / per; t >= 0 && S <= vt; --t) {
+        const int s0 = t * per, e0 = min(s0 + per, nb);
+        const float sn = S + ws.loc[t];
+        if (sn <= vt) {
+          if (ws.first[t] >= 0) { cand = ws.first[t]; whole = true; tj = t; sj = S; }
+          S = sn;
+          continue;
+        }
+        float run = S;
+        for (int b = e0 - 1; b >= s0 && run <= vt; --b) {
+          if (p[b] > 0.f) { cand = b; cand_s = run; whole = false; }
+          run += p[b];
+        }
+        break;
+      }
+      if (whole) {
+        cand_s = sj;
+        for (int b = min(tj * per + per, nb) - 1; b > cand; --b) cand_s += p[b];
+      }
+      idx = cand >= 0 ? cand : ws.lastnz;   // no bar with mass: the row is NaN below
+      frac = fminf(fmaxf(1.0f - (v - cand_s / total) / (p[idx] / total), 0.f), 1.f);
+    } else {
+      idx = ws.qidx[tid];
+      float cprev;
+      if (idx == 0x7fffffff) {  // q beyond the rounded total: the last bar with mass
+        idx = ws.lastnz;
+        cprev = total - p[idx];
+      } else {                  // the owner's serial prefix in front of bar idx
+        const int t = idx / per;
+        cprev = ws.excl[t];
+        for (int b = t * per; b < idx; ++b) cprev += p[b];
+      }
+      const float pn = p[idx] / total;
+      frac = fminf(fmaxf((u - cprev / total) / pn, 0.f), 1.f);
+    }
+    const float left = bz[idx] * bscale + bshift;
+    const float right = bz[idx + 1] * bscale + bshift;
+    const float th = fminf(fmaxf(left + (right - left) * frac, left), right);
+    quant_out[(int64_t)tid * ldq_out] = valid ? th : NAN;
+  }
+}
+
 // resident blocks per CU the k_mix_* kernels are compiled for: 3 (3 waves per SIMD, <= 168
 // VGPRs; the fast path needs 175 at 2 blocks and takes 168 + 32 B of scratch at 3).  The per-row
 // chain of reductions / scans / barriers is latency-bound, so the third block pays: r06 with the
@@ -2966,6 +3174,28 @@ __global__ __launch_bounds__(256) void k_bar_sample(const float* __restrict__ lo
   float th = 0.f, lp = 0.f;
   bar_sample_row(p, borders, 1.0f, 0.0f, nb, u, red, scan, th, lp);
   if (threadIdx.x == 0) out[r] = th;
+}
+
+// Generic criterion.mean / .median / .mode / .icdf(logits): softmax(logits row) -> bar_stats_row
+// on the raw borders; quant_out [n_q][ldq_out].
+__global__ __launch_bounds__(256) void k_bar_stats(const float* __restrict__ logits, const float* __restrict__ borders,
+                                                   int64_t R, int nb, const float* __restrict__ q, int n_q,
+                                                   float* __restrict__ mean_out, float* __restrict__ mode_out,
+                                                   float* __restrict__ quant_out, int64_t ldq_out) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* p = reinterpret_cast<float*>(smem);
+  __shared__ float red[4];
+  __shared__ BarStatsWs ws;
+  const int64_t r = blockIdx.x;
+  const float* lg = logits + r * nb;
+  if ((int)threadIdx.x < n_q) ws.q[threadIdx.x] = q[threadIdx.x];
+  float mx = -INFINITY;
+  for (int b = threadIdx.x; b < nb; b += 256) mx = fmaxf(mx, lg[b]);
+  mx = block_reduce_max(mx, red);
+  for (int b = threadIdx.x; b < nb; b += 256) p[b] = __expf(lg[b] - mx);
+  __syncthreads();
+  bar_stats_row(p, borders, 1.0f, 0.0f, nb, n_q, ws, mean_out ? mean_out + r : nullptr,
+                mode_out ? mode_out + r : nullptr, quant_out ? quant_out + r : nullptr, ldq_out);
 }
 
 // Generic criterion(logits, y): full-support bar NLL.
@@ -3437,6 +3667,17 @@ void launch_mix_nll(const logit_t* logits, int64_t R, int E, int nb, float invT,
   if (R <= 0) return;
   NPFN_MIX_LAUNCH(k_mix_nll, nb, tr, s, logits, R, E, nb, invT, tr, bz, ystats, row_offset, feat, ldf, col, logp_acc,
                   log_eps);
+}
+void launch_mix_log_rows(const logit_t* logits, int64_t ld_rows, int64_t row0, int64_t R, int E, int nb, float invT,
+                         const MixTrans& tr, float* out, int64_t ldo, hipStream_t s) {
+  if (R <= 0) return;
+  NPFN_MIX_LAUNCH(k_mix_log, nb, tr, s, logits + row0 * nb, ld_rows, E, nb, invT, tr, out, ldo);
+}
+void launch_bar_stats(const float* logits, const float* borders, int64_t R, int nb, const float* q, int n_q,
+                      float* mean_out, float* mode_out, float* quant_out, int64_t ldq_out, hipStream_t s) {
+  if (R <= 0) return;
+  hipLaunchKernelGGL(k_bar_stats, dim3((unsigned)R), dim3(256), (size_t)nb * 4, s, logits, borders, R, nb, q, n_q,
+                     mean_out, mode_out, quant_out, ldq_out);
 }
 void launch_bar_sample(const float* logits, const float* borders, int64_t R, int nb, uint64_t seed,
                        uint64_t counter, float* out, hipStream_t s) {

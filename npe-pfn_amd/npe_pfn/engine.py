@@ -86,6 +86,8 @@ SIGNATURES = {
     "npfn_get_borders": (ctypes.c_int, [_vp, _vp, _vp]),
     "npfn_bar_sample": (ctypes.c_int, [_vp, _vp, _i64, _i32, _u64, _u64, _vp, _vp]),
     "npfn_bar_nll": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp]),
+    "npfn_bar_stats": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "npfn_predict_stats": (ctypes.c_int, [_vp, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp]),
     "npfn_ar_sample": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _u64, _i64, _vp, _vp, _f, _vp]),
     "npfn_ar_sample_repeated": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _i64, _u64, _i64, _vp, _vp,
                                                _f, _vp]),
@@ -164,6 +166,22 @@ def _check(lib, rc: int, what: str):
 def _dev_f32(t, device) -> torch.Tensor:
     t = torch.as_tensor(t)
     return t.to(device=device, dtype=torch.float32).contiguous()
+
+
+MAX_QUANTILES = 64  # npfn_bar_stats / npfn_predict_stats take at most this many levels per call
+
+
+def check_quantiles(quantiles) -> list:
+    """The quantile levels of a bar_stats / predict_stats call as a list of floats; ValueError
+    for a level outside [0, 1] (NaN included) or more than MAX_QUANTILES of them.  Pure host
+    logic: callers run it before any engine is touched."""
+    qs = [float(q) for q in np.asarray(list(quantiles) if quantiles is not None else [], dtype=np.float64).reshape(-1)]
+    if len(qs) > MAX_QUANTILES:
+        raise ValueError(f"at most {MAX_QUANTILES} quantiles per call, got {len(qs)}")
+    for q in qs:
+        if not 0.0 <= q <= 1.0:
+            raise ValueError(f"quantiles must lie in [0, 1], got {q!r}")
+    return qs
 
 
 class Engine:
@@ -330,6 +348,56 @@ class Engine:
         _check(self.lib, self.lib.npfn_bar_nll(_ptr(logits), _ptr(borders), _ptr(y), logits.shape[0],
                                                logits.shape[1], _ptr(out), self.stream), "npfn_bar_nll")
         return out
+
+    def _stats_buffers(self, n_rows: int, quantiles, mean: bool, mode: bool):
+        qs = check_quantiles(quantiles)
+        q = torch.tensor(qs, dtype=torch.float32).to(self.device) if qs else None
+        m = torch.empty(n_rows, dtype=torch.float32, device=self.device) if mean else None
+        md = torch.empty(n_rows, dtype=torch.float32, device=self.device) if mode else None
+        qo = torch.empty((len(qs), n_rows), dtype=torch.float32, device=self.device) if qs else None
+        return qs, q, m, md, qo
+
+    @staticmethod
+    def _stats_dict(m, md, qo) -> Dict[str, torch.Tensor]:
+        out = {}
+        if m is not None:
+            out["mean"] = m
+        if md is not None:
+            out["mode"] = md
+        if qo is not None:
+            out["quantiles"] = qo
+        return out
+
+    def bar_stats(self, logits: torch.Tensor, borders: torch.Tensor, quantiles=(), mean: bool = True,
+                  mode: bool = True) -> Dict[str, torch.Tensor]:
+        """npfn_bar_stats: the bar distribution's summaries of each row of ``logits`` [N, n_bars] --
+        ``{"mean": [N], "mode": [N], "quantiles": [len(quantiles), N]}`` on the device (a key is
+        absent when its statistic was not asked for); the median is the quantile 0.5."""
+        logits = _dev_f32(logits, self.device)
+        borders = _dev_f32(borders, self.device)
+        if logits.ndim != 2 or borders.shape != (logits.shape[1] + 1,):
+            raise ValueError(f"bar_stats: logits {tuple(logits.shape)} and borders {tuple(borders.shape)} do not match")
+        qs, q, m, md, qo = self._stats_buffers(logits.shape[0], quantiles, mean, mode)
+        _check(self.lib, self.lib.npfn_bar_stats(_ptr(logits), _ptr(borders), logits.shape[0], logits.shape[1],
+                                                 _ptr(q), len(qs), _ptr(m), _ptr(md), _ptr(qo), self.stream),
+               "npfn_bar_stats")
+        return self._stats_dict(m, md, qo)
+
+    def predict_stats(self, Xq, quantiles=(), mean: bool = True, mode: bool = True) -> Dict[str, torch.Tensor]:
+        """npfn_predict_stats: the summaries of :meth:`bar_stats` for the predictive distribution of
+        every query row, 8192 rows at a time inside the engine: the [N, n_bars] fp32 logits of
+        :meth:`predict_logits` are never allocated."""
+        qs = check_quantiles(quantiles)
+        if self.n_features is None:
+            raise EngineError("predict_stats before fit")
+        Xq = _dev_f32(Xq, self.device)
+        if Xq.ndim != 2 or Xq.shape[1] != self.n_features:
+            raise ValueError(f"predict_stats: X has shape {tuple(Xq.shape)}, fit had {self.n_features} features")
+        qs, q, m, md, qo = self._stats_buffers(Xq.shape[0], qs, mean, mode)
+        _check(self.lib, self.lib.npfn_predict_stats(self.h, _ptr(Xq), Xq.shape[1], Xq.shape[0], _ptr(q), len(qs),
+                                                     _ptr(m), _ptr(md), _ptr(qo), self.stream),
+               "npfn_predict_stats")
+        return self._stats_dict(m, md, qo)
 
     # -------------------------------------------------------------- fused paths
     def ar_sample(self, x_ctx, theta_ctx, x_query, counter: int, with_log_prob: bool = False,

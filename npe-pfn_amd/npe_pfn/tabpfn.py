@@ -194,12 +194,77 @@ class TabPFNRegressor:
         self.engine.fit(X, y)
         return self
 
-    def predict(self, X, output_type: str = "full", quantiles=None):
-        if output_type != "full":
-            raise NotImplementedError(f"output_type={output_type!r}: only 'full' is used by NPE-PFN")
+    OUTPUT_TYPES = ("full", "mean", "median", "mode", "quantiles", "main")
+    DEFAULT_QUANTILES = (0.1, 0.2, 0.3, 0.4, 0.5, 0.6, 0.7, 0.8, 0.9)  # tabpfn's [ext]
+
+    def _stats_request(self, output_type: str, quantiles):
+        """(quantile levels, want mean, want mode) of one predict call; ValueError for an unknown
+        output_type, a level outside [0, 1] or more than 64 levels -- host logic only, checked
+        before the engine is touched."""
+        from .engine import MAX_QUANTILES, check_quantiles
+
+        if output_type not in self.OUTPUT_TYPES:
+            raise ValueError(f"output_type must be one of {list(self.OUTPUT_TYPES)}, got {output_type!r}")
+        qs = check_quantiles(quantiles)
+        if output_type in ("quantiles", "main"):
+            if quantiles is None:
+                qs = list(self.DEFAULT_QUANTILES)
+            if output_type == "main" and len(qs) + 1 > MAX_QUANTILES:
+                raise ValueError(f"output_type='main' takes at most {MAX_QUANTILES - 1} quantiles (the median is "
+                                 f"added to the list), got {len(qs)}")
+        if output_type == "median":
+            qs = [0.5]
+        elif output_type == "main":
+            qs = qs + [0.5]   # the median rides in the same call, last
+        elif output_type != "quantiles":
+            qs = []
+        return qs, output_type in ("mean", "main"), output_type in ("mode", "main")
+
+    def predict_tensor(self, X, output_type: str = "full", quantiles=None):
+        """:meth:`predict` with the results left on the device: a [N] float32 tensor for "mean" /
+        "median" / "mode", a list of [N] tensors for "quantiles", a dict of those for "main",
+        and :meth:`predict`'s own dict for "full"."""
+        qs, want_mean, want_mode = self._stats_request(output_type, quantiles)
         eng = self.engine
-        logits = eng.predict_logits(X)
-        return {"logits": logits, "criterion": BarCriterion(self, eng.borders())}
+        if output_type == "full":
+            logits = eng.predict_logits(X)
+            return {"logits": logits, "criterion": BarCriterion(self, eng.borders())}
+        st = eng.predict_stats(X, qs, mean=want_mean, mode=want_mode)
+        if output_type in ("mean", "mode"):
+            return st[output_type]
+        if output_type == "median":
+            return st["quantiles"][0]
+        if output_type == "quantiles":
+            return list(st["quantiles"].unbind(0)) if qs else []
+        return {"mean": st["mean"], "median": st["quantiles"][-1], "mode": st["mode"],
+                "quantiles": list(st["quantiles"][:-1].unbind(0))}
+
+    def predict(self, X, output_type: str = "full", quantiles=None):
+        """tabpfn's ``predict`` [ext: tabpfn 2.2.1 TabPFNRegressor.predict]:
+
+        * ``"full"`` (the default HERE, and what the reference always passes, with
+          ``quantiles=[]``): ``{"logits", "criterion"}`` only, logits on the device;
+        * ``"mean"``, ``"median"``, ``"mode"``: numpy float32 [N];
+        * ``"quantiles"``: a list with one numpy [N] per level (``quantiles=None``: tabpfn's
+          0.1 ... 0.9);
+        * ``"main"``: ``{"mean", "median", "mode", "quantiles"}`` from one engine call.
+
+        The summaries come from npfn_predict_stats (the half-normal tail bars, never a point in a
+        zero-mass bar) without allocating the [N, n_bars] logits.  Two differences from tabpfn, both kept
+        so that the reference's hot loop does not pay for summaries it never reads: tabpfn's
+        default output_type is ``"mean"``, and its ``"full"`` dict also carries the "main"
+        keys -- ask for ``"main"`` to get them.  ValueError for an unknown output_type, a
+        quantile outside [0, 1] or more than 64 quantiles (63 for "main", which adds the
+        median)."""
+        out = self.predict_tensor(X, output_type, quantiles)
+        if output_type == "full":
+            return out
+        if isinstance(out, dict):
+            return {k: ([q.cpu().numpy() for q in v] if isinstance(v, list) else v.cpu().numpy())
+                    for k, v in out.items()}
+        if isinstance(out, list):
+            return [q.cpu().numpy() for q in out]
+        return out.cpu().numpy()
 
     # ------------------------------------------------------------ fused path
     def ar_sample(self, x_ctx, theta_ctx, x_query, with_log_prob: bool = False, eps: float = 1e-15,
@@ -246,6 +311,35 @@ class BarCriterion:
         out = self._reg.engine.bar_sample(logits, self.borders, self._reg.sample_counter)
         self._reg.sample_counter += 1
         return out.cpu()
+
+    def _stats(self, logits: torch.Tensor, quantiles=(), mean: bool = False, mode: bool = False):
+        logits = torch.as_tensor(logits)
+        st = self._reg.engine.bar_stats(logits, self.borders, quantiles, mean=mean, mode=mode)
+        return {k: v.to(logits.device) for k, v in st.items()}
+
+    def mean(self, logits: torch.Tensor) -> torch.Tensor:
+        """Mean per row (half-normal tail bars), on the device of ``logits``."""
+        return self._stats(logits, mean=True)["mean"]
+
+    def median(self, logits: torch.Tensor) -> torch.Tensor:
+        return self._stats(logits, [0.5])["quantiles"][0]
+
+    def mode(self, logits: torch.Tensor) -> torch.Tensor:
+        """Centre of the densest bar per row."""
+        return self._stats(logits, mode=True)["mode"]
+
+    def icdf(self, logits: torch.Tensor, left_prob) -> torch.Tensor:
+        """Inverse CDF per row at ``left_prob``: [N] for a float, [len(left_prob), N] for a 1-D
+        list of at most 64 levels in [0, 1] (ValueError otherwise)."""
+        lp = torch.as_tensor(left_prob, dtype=torch.float64).cpu()
+        if lp.ndim > 1:
+            raise ValueError(f"icdf: left_prob must be a float or a 1-D list, got shape {tuple(lp.shape)}")
+        levels = lp.reshape(-1).tolist()
+        if not levels:
+            return torch.empty((0, torch.as_tensor(logits).shape[0]), dtype=torch.float32,
+                               device=torch.as_tensor(logits).device)
+        q = self._stats(logits, levels)["quantiles"]
+        return q[0] if lp.ndim == 0 else q
 
     def __call__(self, logits: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         """NLL per row, returned on the device of ``y``."""
