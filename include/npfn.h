@@ -245,6 +245,58 @@ int npfn_box_support(const float* theta, int64_t n_rows, int32_t dim, const floa
 int npfn_compact_rows(const float* src, const uint8_t* mask, int64_t n_rows, int32_t dim,
                       float* dst, int64_t* count_out, void* stream);
 
+/* Box proposals of the restricted prior's rejection sampler (NPE_PFN_RestrictedPrior, reference
+ * restricted_prior.py:8-97; there prior.sample of a BoxUniform inside sbi's rejection loop):
+ * with u = Philox4x32-10 uniform(key = seed, counter = counter + j, row = row_base + i) -- the
+ * u of npfn_bar_sample, the 64-bit row's high word included -- and span_j = fl(high[j] - low[j]),
+ *   out[i, j] = min(fl(low[j] + fl(u * span_j)), high[j]),
+ * every operation rounded to fp32 on its own (no fused multiply-add), so a float32 restatement
+ * is bit-exact (tests/restricted_ref.py).  The min keeps the point inside the closed box that
+ * npfn_box_support accepts when span_j rounded up.  low, high [dim] and out [n_rows, dim] are
+ * DEVICE arrays.  Rows [a, b) with row_base = a are rows a..b-1 of the unsplit call.
+ * Asynchronous; n_rows == 0 launches nothing.
+ * Errors: NPFN_EINVAL for dim < 1, n_rows < 0, row_base < 0, a missing pointer or more than
+ * 2^39 - 256 values in one call. */
+int npfn_box_propose(const float* low, const float* high, int32_t dim, int64_t n_rows, uint64_t seed,
+                     uint64_t counter, int64_t row_base, float* out, void* stream);
+
+/* The restricted prior's accept decision (reference restricted_prior.py:25-28,
+ * `classifier.predict_proba(theta)[:, -1] > acceptance_threshold`): mask_out[i] (uint8, 0 / 1) =
+ * p_i > threshold, strictly, with p_i the LAST class's probability of row i exactly as
+ * npfn_predict_proba returns it -- the same forward, chunking (npfn_set_chunk_rows) and ensemble
+ * mix (npfn_set_average_before_softmax honoured) into an engine-owned window of [chunk rows,
+ * n_classes] probabilities, then one kernel over its last column; bit-equal to column
+ * n_classes - 1 of npfn_predict_proba.  prob_out [n_rows] (may be NULL) receives p_i.
+ * Asynchronous; n_rows == 0 launches nothing.
+ * Errors: NPFN_ESTATE before npfn_fit_classes (or after a regressor fit) or on a partial
+ * estimator range; NPFN_EINVAL for n_rows < 0, ldq < n_features or a missing Xq / mask_out. */
+int npfn_predict_accept(npfn_engine* h, const float* Xq, int64_t ldq, int64_t n_rows, float threshold,
+                        uint8_t* mask_out, float* prob_out, void* stream);
+
+/* One rejection round of the restricted prior over a box (the body of sbi's rejection loop
+ * around restricted_prior.py:25-28, without its two host round trips):
+ *  1. npfn_box_propose(low, high, dim, n_rows, seed, counter, row_base) into engine scratch;
+ *  2. npfn_predict_accept's decision on those rows at `threshold` (dim must be the classifier
+ *     fit's feature count);
+ *  3. the accepted rows, in row order, are appended to theta_out [capacity, dim] from row
+ *     counts[0] on; accepted rows that would land at or past `capacity` are dropped;
+ *  4. counts[0] = min(capacity, counts[0] + accepted); counts[1] += accepted.
+ * counts is a DEVICE int64[2] = {rows stored in theta_out, rows accepted in total}, set to 0 by
+ * the caller before the first round and read by it when it wants to (0 <= counts[0] <= capacity
+ * is the caller's promise).  Rounds with row_base = the rows proposed so far make theta_out the
+ * first `capacity` accepted rows of the Philox row stream, whatever the sizes of the rounds (the
+ * forward is batch-invariant).  The append is one workgroup taking 1024 rows per pass in order:
+ * deterministic, no floating-point atomics, no workgroup waiting on another.
+ * n_rows == 0 launches nothing; counts[0] == capacity leaves theta_out untouched (the round
+ * still counts its accepted rows into counts[1]).  Asynchronous; the scratch for proposals,
+ * flags and probabilities is engine-owned and grows on demand (growing waits on the stream).
+ * Errors: NPFN_ESTATE as for npfn_predict_accept; NPFN_EINVAL for dim != n_features, n_rows < 0,
+ * capacity < 0, row_base < 0, a missing low / high / counts, or a missing theta_out with
+ * capacity > 0; NPFN_ENOMEM when the scratch does not fit. */
+int npfn_restricted_box_round(npfn_engine* h, const float* low, const float* high, int32_t dim, float threshold,
+                              int64_t n_rows, uint64_t seed, uint64_t counter, int64_t row_base, float* theta_out,
+                              int64_t capacity, int64_t* counts, void* stream);
+
 /* K12 standardized-Euclidean context filter (support_posterior.py:357-369):
  * idx_out[0:k] = indices of the k rows of x [n_rows, dim] closest to obs in
  * z-scored Euclidean distance, ascending (ties by lower index). */

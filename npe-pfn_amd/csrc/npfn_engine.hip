@@ -182,6 +182,9 @@ struct npfn_engine {
   DevBuf joint, feat, logp;
   DevBuf pu;  // [n_unique][nb] step-0 mixtures of npfn_ar_sample_repeated
   DevBuf mixlog, borders;  // npfn_predict_stats: [kStatsRows][nb] mixture logits of a row window, [nb + 1] borders
+  // npfn_predict_accept / npfn_restricted_box_round: [chunk rows][n_classes] probabilities of a
+  // chunk; [n_rows][dim] proposals and [n_rows] accept flags of a round
+  DevBuf rp_probs, rp_theta, rp_mask;
   int64_t chunk_rows = 16384;
   // estimator set of fits and forwards (npfn_set_estimator_set): estimators e0 + es * i,
   // i < ne, of cfg.n_estimators; a partial set is the estimator-parallel multi-GPU split
@@ -1476,7 +1479,7 @@ int npfn_engine_destroy(npfn_engine* h) {
   h->wmain.release();
   h->wside.release();
   DevBuf* bufs[] = {&h->dh,      &h->logits, &h->tgt,
-                    &h->joint, &h->feat,     &h->logp, &h->pu, &h->mixlog, &h->borders, &h->views, &h->ftype, &h->ett,     &h->fp_salt};
+                    &h->joint, &h->feat,     &h->logp, &h->pu, &h->mixlog, &h->borders, &h->rp_probs, &h->rp_theta, &h->rp_mask, &h->views, &h->ftype, &h->ett,     &h->fp_salt};
   for (DevBuf* b : bufs) free_buf(*b);
   delete h;
   return NPFN_OK;
@@ -1530,6 +1533,76 @@ int npfn_predict_proba(npfn_engine* h, const float* Xq, int64_t ldq, int64_t n_r
     ProfGuard g(h, P_CLS_MIX, 0.0, (double)E * rows * nb * sizeof(logit_t) + (double)rows * h->f->ncls * 4, s);
     launch_cls_mix((const logit_t*)h->logits.p, rows, E, nb, h->f->ncls, invT, (const int*)h->f->cperm.p,
                    h->avg_before_softmax, probs + r0 * h->f->ncls, h->f->ncls, s);
+  }
+  HIPCHK(hipGetLastError());
+  return NPFN_OK;
+}
+
+// npfn_predict_proba's chunk loop into the engine's probability window, then the threshold on the
+// last class: the probabilities are those of npfn_predict_proba bit for bit (same forward, same
+// k_cls_mix launch per chunk; only the output buffer differs)
+static int accept_rows(npfn_engine* h, const float* Xq, int64_t ldq, int64_t n_rows, float threshold, uint8_t* mask,
+                       float* prob_out, hipStream_t s) {
+  const int E = h->cfg.n_estimators, nb = h->cfg.n_bars, K = h->f->ncls;
+  const float invT = 1.0f / h->cfg.softmax_temperature;
+  RCHK(ensure(h->rp_probs, (size_t)std::min(h->chunk_rows, n_rows) * K * sizeof(float), s));
+  for (int64_t r0 = 0; r0 < n_rows; r0 += h->chunk_rows) {
+    const int64_t rows = std::min(h->chunk_rows, n_rows - r0);
+    RCHK(predict_logits_chunk(h, Xq + r0 * ldq, ldq, rows, s));
+    {
+      ProfGuard g(h, P_CLS_MIX, 0.0, (double)E * rows * nb * sizeof(logit_t) + (double)rows * K * 4, s);
+      launch_cls_mix((const logit_t*)h->logits.p, rows, E, nb, K, invT, (const int*)h->f->cperm.p,
+                     h->avg_before_softmax, (float*)h->rp_probs.p, K, s);
+    }
+    ProfGuard g(h, P_OTHER, 0.0, (double)rows * (4 + 1 + (prob_out ? 4 : 0)), s);
+    launch_accept_last((const float*)h->rp_probs.p, rows, K, threshold, mask + r0, prob_out ? prob_out + r0 : nullptr,
+                       s);
+  }
+  HIPCHK(hipGetLastError());
+  return NPFN_OK;
+}
+
+int npfn_predict_accept(npfn_engine* h, const float* Xq, int64_t ldq, int64_t n_rows, float threshold,
+                        uint8_t* mask_out, float* prob_out, void* stream) {
+  RCHK(check_engine(h));
+  if (!h->f->fitted || h->f->ncls == 0) return fail(NPFN_ESTATE, "predict_accept before fit_classes");
+  RCHK(need_full_range(h, "predict_accept"));
+  if (n_rows < 0) return fail(NPFN_EINVAL, "predict_accept: n_rows < 0");
+  if (!Xq || !mask_out) return fail(NPFN_EINVAL, "predict_accept: null pointer");
+  if (ldq < h->f->F) return fail(NPFN_EINVAL, "predict_accept: ldq < n_features");
+  if (n_rows == 0) return NPFN_OK;
+  return accept_rows(h, Xq, ldq, n_rows, threshold, mask_out, prob_out, (hipStream_t)stream);
+}
+
+int npfn_restricted_box_round(npfn_engine* h, const float* low, const float* high, int32_t dim, float threshold,
+                              int64_t n_rows, uint64_t seed, uint64_t counter, int64_t row_base, float* theta_out,
+                              int64_t capacity, int64_t* counts, void* stream) {
+  RCHK(check_engine(h));
+  if (!h->f->fitted || h->f->ncls == 0) return fail(NPFN_ESTATE, "restricted_box_round before fit_classes");
+  RCHK(need_full_range(h, "restricted_box_round"));
+  if (dim != h->f->F)
+    return fail(NPFN_EINVAL, "restricted_box_round: dim " + std::to_string(dim) + " != the classifier fit's " +
+                                 std::to_string(h->f->F) + " features");
+  if (n_rows < 0 || capacity < 0 || row_base < 0)
+    return fail(NPFN_EINVAL, "restricted_box_round: need n_rows >= 0, capacity >= 0 and row_base >= 0");
+  if (!low || !high || !counts || (capacity > 0 && !theta_out))
+    return fail(NPFN_EINVAL, "restricted_box_round: null pointer");
+  if (n_rows == 0) return NPFN_OK;
+  if (n_rows > (0x7fffffffll * 256) / dim)
+    return fail(NPFN_EINVAL, "restricted_box_round: too many values for one launch");
+  hipStream_t s = (hipStream_t)stream;
+  RCHK(ensure(h->rp_theta, (size_t)n_rows * dim * sizeof(float), s));
+  RCHK(ensure(h->rp_mask, (size_t)n_rows, s));
+  float* prop = (float*)h->rp_theta.p;
+  uint8_t* mask = (uint8_t*)h->rp_mask.p;
+  {
+    ProfGuard g(h, P_OTHER, 0.0, (double)n_rows * dim * 4, s);
+    launch_box_propose(low, high, dim, n_rows, seed, counter, (uint64_t)row_base, prop, s);
+  }
+  RCHK(accept_rows(h, prop, dim, n_rows, threshold, mask, nullptr, s));
+  {
+    ProfGuard g(h, P_OTHER, 0.0, (double)n_rows * (1 + dim * 8), s);
+    launch_append_rows(prop, mask, n_rows, dim, theta_out, capacity, counts, s);
   }
   HIPCHK(hipGetLastError());
   return NPFN_OK;

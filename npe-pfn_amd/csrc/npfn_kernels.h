@@ -305,5 +305,15 @@ void launch_copy_cols(const float* src, int64_t lds, float* dst, int64_t ldd, in
 void launch_fill(float* dst, int64_t n, float v, hipStream_t s);
 void launch_box_support(const float* th, int64_t n, int dim, const float* lo, const float* hi, uint8_t* mask,
                         hipStream_t s);
+// npfn_restricted.hip: one rejection round of the restricted prior.  Proposals out [n][dim] of
+// the box [low, high] at Philox rows row_base + i, counters counter + j; mask / prob_out
+// (nullable) from column K - 1 of probs [n][K] against thr (strict >); accepted rows of src
+// appended in order at dst row counts[0] up to capacity, counts = {stored, accepted} (int64[2])
+void launch_box_propose(const float* low, const float* high, int dim, int64_t n, uint64_t seed, uint64_t counter,
+                        uint64_t row_base, float* out, hipStream_t s);
+void launch_accept_last(const float* probs, int64_t n, int K, float thr, uint8_t* mask, float* prob_out,
+                        hipStream_t s);
+void launch_append_rows(const float* src, const uint8_t* mask, int64_t n, int dim, float* dst, int64_t capacity,
+                        int64_t* counts, hipStream_t s);
 
 }  // namespace npfn

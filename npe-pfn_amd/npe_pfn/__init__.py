@@ -2,16 +2,18 @@
 
 Same public names as the reference package (npe_pfn/__init__.py:1-12), so
 ``from npe_pfn import TabPFN_Based_NPE_PFN, TabPFN_Based_Uncond_Estimator,
-run_tsnpe_pfn`` keeps working with
+NPE_PFN_RestrictedPrior, run_tsnpe_pfn`` keeps working with
 this directory (``npe-pfn_amd``) on ``sys.path``.  The TabPFN forward runs in
 the HIP engine ``npe_pfn/_lib/libnpfn.so`` (C-ABI: include/npfn.h).
 """
 
 from npe_pfn.npe_pfn import NPE_PFN_Core, TabPFN_Based_NPE_PFN, TabPFN_Based_Uncond_Estimator
+from npe_pfn.restricted_prior import NPE_PFN_RestrictedPrior
 from npe_pfn.tsnpe_pfn import run_tsnpe_pfn
 
 __all__ = [
     "NPE_PFN_Core",
+    "NPE_PFN_RestrictedPrior",
     "TabPFN_Based_NPE_PFN",
     "TabPFN_Based_Uncond_Estimator",
     "run_tsnpe_pfn",

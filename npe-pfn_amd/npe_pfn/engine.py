@@ -95,6 +95,10 @@ SIGNATURES = {
     "npfn_ar_log_prob_repeated": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _f, _vp]),
     "npfn_box_support": (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     "npfn_compact_rows": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "npfn_box_propose": (ctypes.c_int, [_vp, _vp, _i32, _i64, _u64, _u64, _i64, _vp, _vp]),
+    "npfn_predict_accept": (ctypes.c_int, [_vp, _vp, _i64, _i64, _f, _vp, _vp, _vp]),
+    "npfn_restricted_box_round": (ctypes.c_int, [_vp, _vp, _vp, _i32, _f, _i64, _u64, _u64, _i64, _vp, _i64, _vp,
+                                                 _vp]),
     "npfn_filter_stdeuclid": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i64, _vp, _vp]),
     "npfn_sir_select": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _u64, _u64, _i64, _vp, _i32, _vp, _vp, _vp, _vp]),
     "npfn_kmeans_fit": (ctypes.c_int, [_vp, _i64, _i32, _i32, _u64, _i32, _f, _vp, _vp, _vp, _vp, _vp]),
@@ -488,6 +492,65 @@ class Engine:
         _check(self.lib, self.lib.npfn_compact_rows(_ptr(src), _ptr(m), src.shape[0], src.shape[1], _ptr(dst),
                                                     _ptr(cnt), self.stream), "npfn_compact_rows")
         return dst[: int(cnt.item())]
+
+    # ------------------------------------------- restricted prior (npfn_restricted.hip)
+    def box_bounds(self, low, high, dim: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Bounds on the device, expanded to ``dim`` as :meth:`box_support` does."""
+        low = torch.broadcast_to(_dev_f32(low, self.device).reshape(-1), (dim,)).contiguous()
+        high = torch.broadcast_to(_dev_f32(high, self.device).reshape(-1), (dim,)).contiguous()
+        return low, high
+
+    def box_propose(self, n_rows: int, dim: int, low, high, counter: int, row_base: int = 0,
+                    seed: Optional[int] = None) -> torch.Tensor:
+        """[n_rows, dim] points of the box [low, high] at rows ``row_base + i`` of the Philox row
+        stream (npfn_box_propose); ``seed`` defaults to the engine's random_state."""
+        n_rows, dim = int(n_rows), int(dim)
+        if n_rows < 0 or dim < 1:
+            raise ValueError(f"box_propose: need n_rows >= 0 and dim >= 1, got {n_rows}, {dim}")
+        low, high = self.box_bounds(low, high, dim)
+        out = torch.empty((n_rows, dim), dtype=torch.float32, device=self.device)
+        seed = self.random_state if seed is None else int(seed)
+        _check(self.lib, self.lib.npfn_box_propose(_ptr(low), _ptr(high), dim, n_rows, seed & 0xFFFFFFFFFFFFFFFF,
+                                                   int(counter) & 0xFFFFFFFFFFFFFFFF, int(row_base), _ptr(out),
+                                                   self.stream), "npfn_box_propose")
+        return out
+
+    def predict_accept(self, Xq, threshold: float, return_prob: bool = False):
+        """Bool mask ``predict_proba(Xq)[:, -1] > threshold`` on the device (npfn_predict_accept);
+        with ``return_prob`` also that last-class probability, bit-equal to predict_proba's."""
+        Xq = _dev_f32(Xq, self.device)
+        if Xq.ndim != 2 or (self.n_features is not None and Xq.shape[1] != self.n_features):
+            raise ValueError(f"predict_accept: X has shape {tuple(Xq.shape)}, fit had {self.n_features} features")
+        mask = torch.empty(Xq.shape[0], dtype=torch.uint8, device=self.device)
+        prob = torch.empty(Xq.shape[0], dtype=torch.float32, device=self.device) if return_prob else None
+        _check(self.lib, self.lib.npfn_predict_accept(self.h, _ptr(Xq), Xq.shape[1], Xq.shape[0], float(threshold),
+                                                      _ptr(mask), _ptr(prob), self.stream), "npfn_predict_accept")
+        return (mask.bool(), prob) if return_prob else mask.bool()
+
+    def restricted_box_round(self, low, high, threshold: float, n_rows: int, counter: int, row_base: int,
+                             theta_out: torch.Tensor, counts: torch.Tensor, capacity: Optional[int] = None,
+                             seed: Optional[int] = None) -> None:
+        """One rejection round on the device (npfn_restricted_box_round): ``n_rows`` box proposals at
+        Philox rows ``row_base + i``, the classifier's accept decision, and the accepted rows
+        appended in order to ``theta_out`` [>= capacity, dim] at ``counts[0]``.  ``counts`` is a
+        device int64[2] = (stored, accepted); nothing is read back here."""
+        if (theta_out.ndim != 2 or theta_out.dtype != torch.float32 or theta_out.device != self.device
+                or not theta_out.is_contiguous()):
+            raise ValueError("restricted_box_round: theta_out must be a contiguous float32 [capacity, dim] tensor "
+                             "on the engine's device")
+        if (counts.dtype != torch.int64 or counts.numel() != 2 or counts.device != self.device
+                or not counts.is_contiguous()):
+            raise ValueError("restricted_box_round: counts must be a contiguous int64[2] on the engine's device")
+        dim = theta_out.shape[1]
+        capacity = theta_out.shape[0] if capacity is None else int(capacity)
+        if not 0 <= capacity <= theta_out.shape[0]:
+            raise ValueError(f"restricted_box_round: capacity {capacity} outside theta_out's {theta_out.shape[0]} rows")
+        low, high = self.box_bounds(low, high, dim)
+        seed = self.random_state if seed is None else int(seed)
+        _check(self.lib, self.lib.npfn_restricted_box_round(
+            self.h, _ptr(low), _ptr(high), dim, float(threshold), int(n_rows), seed & 0xFFFFFFFFFFFFFFFF,
+            int(counter) & 0xFFFFFFFFFFFFFFFF, int(row_base), _ptr(theta_out), capacity, _ptr(counts), self.stream),
+            "npfn_restricted_box_round")
 
     def filter_stdeuclid(self, x: torch.Tensor, obs: torch.Tensor, k: int) -> torch.Tensor:
         x = _dev_f32(x, self.device)
