@@ -154,6 +154,30 @@ int npfn_bar_sample(const float* logits, const float* borders, int64_t n_rows, i
 int npfn_bar_nll(const float* logits, const float* borders, const float* y, int64_t n_rows,
                  int32_t n_bars, float* out, void* stream);
 
+/* criterion.cdf(logits, y): the CDF of the full-support bar distribution, the integral of exactly
+ * the density whose negative log npfn_bar_nll returns (half-normal tail bars included):
+ * out[i] = F(y_i) under row i of logits [n_rows, n_bars].  With p = softmax(logits row), borders
+ * b[0..n_bars], w_j = b[j+1] - b[j], HM = 0.6744897501960817 and j the bucket of y by the NLL's
+ * rule (searchsorted(b, y, left) - 1, the two end-border fix-ups, clamped to [0, n_bars-1]):
+ *   F = sum_{i<j} p_i + p_j frac,
+ *  - inner bars: frac = clamp((y - b[j]) / w_j, 0, 1);
+ *  - left tail bar (j = 0), a half-normal hanging left from b[1] with scale s0 = w_0 / HM:
+ *    frac = erfc(max(b[1] - y, 0) / (s0 sqrt 2)), so F(b[0]) = p_0 / 2 and F(-inf) = 0;
+ *  - right tail bar (j = n_bars-1), s1 = w_last / HM: frac = erf(max(y - b[n_bars-1], 0) / (s1 sqrt 2));
+ *  - w_j == 0: frac = 1.
+ * The mass left and right of bar j are both summed (fp32 block sums) and the result is formed in
+ * fp64 from the smaller side -- (S_left + p_j frac) / total if S_left <= S_right, else
+ * 1 - (S_right + p_j (1 - frac)) / total with 1 - frac from the complementary error function in
+ * the tails -- so the upper tail keeps its relative precision (as npfn_bar_stats' high quantiles).
+ * y = NaN or a row without a finite logit gives NaN; y = -inf gives 0, y = +inf gives 1.
+ * Note: tabpfn's sampler interpolates LINEARLY inside the two tail bars while its density there is
+ * half-normal; npfn_bar_sample and the icdf of npfn_bar_stats keep that, so icdf(cdf(y)) == y
+ * holds on the inner bars only.
+ * Asynchronous; n_rows == 0 launches nothing.
+ * Errors: NPFN_EINVAL for n_bars < 2, n_rows < 0 or a missing pointer. */
+int npfn_bar_cdf(const float* logits, const float* borders, const float* y, int64_t n_rows, int32_t n_bars,
+                 float* out, void* stream);
+
 /* criterion.mean(logits), .median(logits), .mode(logits) and .icdf(logits, q) [ext: tabpfn 2.2.1
  * FullSupportBarDistribution] of each row of logits [n_rows, n_bars] in one pass.  With borders
  * b[0..n_bars], widths w_j = b[j+1] - b[j], p = softmax(logits row), HM = the half-normal median
@@ -234,6 +258,26 @@ int npfn_ar_log_prob_repeated(npfn_engine* h, const float* x_ctx, const float* t
                               int32_t dim_x, int32_t dim_theta, const float* x_unique, int64_t n_unique,
                               const float* theta, int64_t n_rows, float* log_prob_out, float eps,
                               void* stream);
+
+/* The teacher-forced pass of npfn_ar_log_prob / npfn_ar_log_prob_repeated with its per-step
+ * results kept (NPE_PFN_Core.log_prob_batched / pit_batched; the reference declares
+ * log_prob_batched and leaves it unimplemented, npe_pfn.py:457-460).  x_unique [n_unique, dim_x],
+ * query row i = x_unique[i / (n_rows / n_unique)], n_unique dividing n_rows: n_unique == n_rows is
+ * the plain case (npfn_ar_log_prob's path), otherwise step 0 runs its forward once per distinct
+ * row (npfn_ar_log_prob_repeated's path).  theta [n_rows, dim_theta].
+ *  - logp_steps [n_rows, dim_theta]: [i, k] = step k's log density of theta[i, k] given x and
+ *    theta[i, :k], -inf replaced by log(eps) -- the same arithmetic on the same mixture as
+ *    npfn_ar_log_prob, so summing the columns in order in fp32 gives its result bit for bit;
+ *  - cdf_steps [n_rows, dim_theta]: [i, k] = npfn_bar_cdf's F(theta[i, k]) of that step's mixture
+ *    on that step's borders -- the probability integral transform u_k = F_k(theta_k | x,
+ *    theta_<k), uniform exactly when conditional k is calibrated.
+ * Either output may be NULL (it is skipped), not both.  Fit reuse (npfn_set_fit_token), chunking
+ * (npfn_set_chunk_rows) and npfn_set_average_before_softmax as for npfn_ar_log_prob.  Asynchronous.
+ * Errors: NPFN_ESTATE on a partial estimator range; NPFN_EINVAL for bad dimensions, a missing
+ * input, n_unique < 1 or not dividing n_rows, or both outputs NULL. */
+int npfn_ar_score(npfn_engine* h, const float* x_ctx, const float* theta_ctx, int64_t n_ctx, int32_t dim_x,
+                  int32_t dim_theta, const float* x_unique, int64_t n_unique, const float* theta, int64_t n_rows,
+                  float* logp_steps, float* cdf_steps, float eps, void* stream);
 
 /* K9: prior-support check of a box prior (npe_pfn.py:581-600 with
  * BoxUniform): mask[i] = all_j(low_j <= theta[i,j] <= high_j). */

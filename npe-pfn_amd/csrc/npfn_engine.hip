@@ -1362,6 +1362,60 @@ int ar_log_prob_impl(npfn_engine* h, const float* x_ctx, const float* theta_ctx,
   return NPFN_OK;
 }
 
+// npfn_ar_score: ar_log_prob_impl's teacher-forced pass (n_unique = 0: x_query [n_rows][dim_x];
+// else the repeated rows' path) with every step's log density and CDF written to column k of
+// logp_steps / cdf_steps [n_rows][dim_theta] (k_mix_score / k_group_score) instead of summed.
+int ar_score_impl(npfn_engine* h, const float* x_ctx, const float* theta_ctx, int64_t n_ctx, int dim_x, int dim_theta,
+                  const float* x_query, int64_t n_unique, const float* theta, int64_t n_rows, float* logp_steps,
+                  float* cdf_steps, float eps, hipStream_t s) {
+  if (!theta) return fail(NPFN_EINVAL, "ar_score: null theta");
+  if (!logp_steps && !cdf_steps) return fail(NPFN_EINVAL, "ar_score: both outputs are null");
+  RCHK(need_full_range(h, "ar_score"));
+  RCHK(ensure_pipelines(h, false));
+  const int64_t per = n_unique > 0 ? n_rows / n_unique : 1;
+  RCHK(ar_common_setup(h, x_ctx, theta_ctx, n_ctx, dim_x, dim_theta, x_query, n_rows, s, per));
+  const int Ft = dim_x + dim_theta, E = h->cfg.n_estimators, nb = h->cfg.n_bars;
+  const float invT = 1.0f / h->cfg.softmax_temperature;
+  const float log_eps = logf(eps);
+  float* joint = (float*)h->joint.p;
+  float* feat = (float*)h->feat.p;
+  launch_copy_cols(theta, dim_theta, feat, Ft, n_rows, dim_theta, dim_x, s);
+  bool reuse = false, piped = false;
+  begin_ar_fits(h, n_ctx, dim_x, dim_theta, reuse);
+  if (!reuse) RCHK(ar_prefit(h, joint, Ft, n_ctx, dim_x, dim_theta, s, piped));
+  for (int k = 0; k < dim_theta; ++k) {
+    const int F = dim_x + k;
+    float* lpk = logp_steps ? logp_steps + k : nullptr;
+    float* cdk = cdf_steps ? cdf_steps + k : nullptr;
+    h->f = step_fit(h, k);
+    if (!reuse) RCHK(ar_step_fit(h, joint, Ft, n_ctx, dim_x, dim_theta, k, piped, s));
+    if (k == 0 && n_unique > 0 && n_rows > 0) {
+      RCHK(ensure(h->pu, (size_t)n_unique * nb * sizeof(float), s));
+      float* pu = (float*)h->pu.p;
+      for (int64_t u0 = 0; u0 < n_unique; u0 += h->chunk_rows) {
+        const int64_t rows = std::min(h->chunk_rows, n_unique - u0);
+        RCHK(predict_logits_chunk(h, x_query + u0 * dim_x, dim_x, rows, s));
+        ProfGuard g(h, P_MIX_NLL, 0.0, (double)E * rows * nb * sizeof(logit_t), s);
+        launch_mix_prob((const logit_t*)h->logits.p, rows, E, nb, invT, h->mixtrans(), pu + u0 * nb, s);
+      }
+      ProfGuard g(h, P_MIX_NLL, 0.0, (double)n_rows * nb * 4, s);
+      launch_group_score(pu, per, n_rows, nb, h->bz, (const float*)h->f->ystats.p, 0, feat, Ft, F, lpk, cdk, dim_theta,
+                         log_eps, s);
+      continue;
+    }
+    for (int64_t r0 = 0; r0 < n_rows; r0 += h->chunk_rows) {
+      const int64_t rows = std::min(h->chunk_rows, n_rows - r0);
+      RCHK(predict_logits_chunk(h, feat + r0 * Ft, Ft, rows, s));
+      ProfGuard g(h, P_MIX_NLL, 0.0, (double)E * rows * nb * sizeof(logit_t), s);
+      launch_mix_score((const logit_t*)h->logits.p, rows, E, nb, invT, h->mixtrans(), h->bz, (const float*)h->f->ystats.p, r0,
+                       feat, Ft, F, lpk, cdk, dim_theta, log_eps, s);
+    }
+  }
+  end_ar_fits(h, n_ctx, dim_x, dim_theta);
+  HIPCHK(hipGetLastError());
+  return NPFN_OK;
+}
+
 }  // namespace
 
 // =================================================================== C-ABI
@@ -1743,6 +1797,27 @@ int npfn_ar_log_prob_repeated(npfn_engine* h, const float* x_ctx, const float* t
     return fail(NPFN_EINVAL, "ar_log_prob_repeated: need n_unique >= 1 dividing n_rows");
   return ar_log_prob_impl(h, x_ctx, theta_ctx, n_ctx, dim_x, dim_theta, x_unique, n_unique, theta, n_rows,
                           log_prob_out, eps, (hipStream_t)stream);
+}
+
+int npfn_ar_score(npfn_engine* h, const float* x_ctx, const float* theta_ctx, int64_t n_ctx, int32_t dim_x,
+                  int32_t dim_theta, const float* x_unique, int64_t n_unique, const float* theta, int64_t n_rows,
+                  float* logp_steps, float* cdf_steps, float eps, void* stream) {
+  RCHK(check_engine(h));
+  if (n_unique < 1 || n_rows < 0 || n_rows % n_unique != 0)
+    return fail(NPFN_EINVAL, "ar_score: need n_unique >= 1 dividing n_rows");
+  // n_unique == n_rows: every query row is its own (npfn_ar_log_prob's path)
+  return ar_score_impl(h, x_ctx, theta_ctx, n_ctx, dim_x, dim_theta, x_unique, n_unique == n_rows ? 0 : n_unique, theta,
+                       n_rows, logp_steps, cdf_steps, eps, (hipStream_t)stream);
+}
+
+int npfn_bar_cdf(const float* logits, const float* borders, const float* y, int64_t n_rows, int32_t n_bars,
+                 float* out, void* stream) {
+  if (n_bars < 2 || n_rows < 0) return fail(NPFN_EINVAL, "bar_cdf: need n_bars >= 2 and n_rows >= 0");
+  if (n_rows == 0) return NPFN_OK;
+  if (!logits || !borders || !y || !out) return fail(NPFN_EINVAL, "bar_cdf: null pointer");
+  launch_bar_cdf(logits, borders, y, n_rows, n_bars, out, (hipStream_t)stream);
+  HIPCHK(hipGetLastError());
+  return NPFN_OK;
 }
 
 int npfn_ar_fit_begin(npfn_engine* h, const float* x_ctx, const float* theta_ctx, int64_t n_ctx, int32_t dim_x,

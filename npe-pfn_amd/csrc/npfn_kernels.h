@@ -286,6 +286,18 @@ void launch_group_nll(const float* p_rows, int64_t per, int64_t R, int nb, const
 void launch_mix_nll(const logit_t* logits, int64_t R, int E, int nb, float invT, const MixTrans& tr, const float* bz,
                     const float* ystats, int64_t row_offset, const float* feat, int64_t ldf, int col,
                     float* logp_acc, float log_eps, hipStream_t s);
+// launch_mix_nll / launch_group_nll with the step's outputs kept per row (npfn_ar_score): row r
+// writes its log density (-inf -> log_eps) to logp_out[(row_offset + r) * ldo] and the mixture's
+// CDF at its target to cdf_out[(row_offset + r) * ldo]; either may be null
+void launch_group_score(const float* p_rows, int64_t per, int64_t R, int nb, const float* bz, const float* ystats,
+                        int64_t row_offset, const float* feat, int64_t ldf, int col, float* logp_out, float* cdf_out,
+                        int64_t ldo, float log_eps, hipStream_t s);
+void launch_mix_score(const logit_t* logits, int64_t R, int E, int nb, float invT, const MixTrans& tr, const float* bz,
+                      const float* ystats, int64_t row_offset, const float* feat, int64_t ldf, int col,
+                      float* logp_out, float* cdf_out, int64_t ldo, float log_eps, hipStream_t s);
+// out[r] = CDF of softmax(logits row r) on borders at y[r] (the full-support bar distribution)
+void launch_bar_cdf(const float* logits, const float* borders, const float* y, int64_t R, int nb, float* out,
+                    hipStream_t s);
 // launch_mix_log over rows [row0, row0 + R) of logits [E][ld_rows][nb]; out row r = row row0 + r
 void launch_mix_log_rows(const logit_t* logits, int64_t ld_rows, int64_t row0, int64_t R, int E, int nb, float invT,
                          const MixTrans& tr, float* out, int64_t ldo, hipStream_t s);

@@ -3155,6 +3155,143 @@ __global__ __launch_bounds__(256) void k_group_nll(const float* __restrict__ p_r
   if (threadIdx.x == 0) logp_acc[row_offset + r] += (lpf == -INFINITY) ? log_eps : lpf;
 }
 
+// CDF of the full-support bar distribution at th: the integral of the density whose log
+// bar_logp_row returns.  bar_cdf_bucket is the NLL's bucket rule (searchsorted left - 1, the two
+// end-border fix-ups, clamped; NaN lands in bar 0 and is answered by bar_cdf_finish); every thread
+// may call it.  bar_cdf_finish, one thread per row in fp64: sl / sr = the (unnormalized) mass of
+// the bars left / right of bar j, pj that of bar j; the fraction of bar j left of th is linear in
+// an inner bar, erfc / erf of the half-normal tails (scales w / NPFN_HALFNORMAL_MEDIAN, as in the
+// NLL) in the two end bars, 1 in a bar of width 0; the result is formed from the smaller side, so
+// that the upper tail is not lost to the rounding of 1 - (a long sum from the left).  NaN for a
+// NaN th or a total that is not a positive finite number; 0 / 1 at th = -inf / +inf.
+__device__ __forceinline__ int bar_cdf_bucket(const float* __restrict__ bz, float bs, float bsh, int nb, float th) {
+  int lo = 0, hi = nb + 1;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (bz[mid] * bs + bsh < th) lo = mid + 1; else hi = mid;
+  }
+  int j = lo - 1;
+  if (th == bz[0] * bs + bsh) j = 0;
+  if (th == bz[nb] * bs + bsh) j = nb - 1;
+  return min(max(j, 0), nb - 1);
+}
+__device__ float bar_cdf_finish(float sl, float pj, float sr, int j, int nb, const float* __restrict__ bz, float bs,
+                                float bsh, float th) {
+  const double tot = ((double)sl + (double)pj) + (double)sr;
+  if (th != th || !(tot > 0.0) || !(tot < (double)INFINITY)) return NAN;
+  if (th == -INFINITY) return 0.f;
+  if (th == INFINITY) return 1.f;
+  const double left = (double)(bz[j] * bs + bsh), right = (double)(bz[j + 1] * bs + bsh);
+  const double w = right - left;
+  double frac = 1.0, rest = 0.0;   // the share of bar j left / right of th
+  if (w > 0.0) {
+    if (j == 0) {                  // half-normal hanging left from b[1]
+      const double z = fmax(right - (double)th, 0.0) / (w / NPFN_HALFNORMAL_MEDIAN * M_SQRT2);
+      frac = erfc(z);
+      rest = erf(z);
+    } else if (j == nb - 1) {      // half-normal hanging right from b[nb - 1]
+      const double z = fmax((double)th - left, 0.0) / (w / NPFN_HALFNORMAL_MEDIAN * M_SQRT2);
+      frac = erf(z);
+      rest = erfc(z);
+    } else {
+      frac = fmin(fmax(((double)th - left) / w, 0.0), 1.0);
+      rest = 1.0 - frac;
+    }
+  }
+  if (sl <= sr) return (float)(((double)sl + (double)pj * frac) / tot);
+  return (float)(1.0 - ((double)sr + (double)pj * rest) / tot);
+}
+// The masses left and right of bar j of the mixture p[0..nb) in LDS, then bar_cdf_finish; every
+// thread calls it, thread 0's result is the one used.
+__device__ float bar_cdf_row(const float* __restrict__ p, int nb, const float* __restrict__ bz, float bs, float bsh,
+                             float th, float* red) {
+  const int j = bar_cdf_bucket(bz, bs, bsh, nb, th);
+  float sl = 0.f, sr = 0.f;
+  for (int b = threadIdx.x; b < nb; b += 256) {
+    const float v = p[b];
+    if (b < j) sl += v;
+    if (b > j) sr += v;
+  }
+  sl = block_reduce_sum(sl, red);
+  sr = block_reduce_sum(sr, red);
+  if (threadIdx.x != 0) return 0.f;
+  return bar_cdf_finish(sl, p[j], sr, j, nb, bz, bs, bsh, th);
+}
+
+// Teacher-forced step with its per-step outputs (npfn_ar_score): k_mix_nll's mixture and log
+// density (the same bar_logp_row on the same LDS mixture), written to logp_out instead of added
+// to an accumulator, and the CDF of that mixture at the target (the PIT value).  Either output
+// may be null; row r writes element (row_offset + r) * ldo of each.
+template <int NV>  // 0: generic path, else the fast path with NV float4 per thread
+__global__ __launch_bounds__(256, NPFN_MIX_MINB) void k_mix_score(const logit_t* __restrict__ logits, int64_t R, int E, int nb,
+                                                   float invT, MixTrans tr, const float* __restrict__ bz,
+                                                   const float* __restrict__ ystats, int64_t row_offset,
+                                                   const float* __restrict__ feat, int64_t ldf, int col,
+                                                   float* __restrict__ logp_out, float* __restrict__ cdf_out,
+                                                   int64_t ldo, float log_eps) {
+  NPFN_MIX_SMEM_VIEW
+  const int64_t r = blockIdx.x;
+  NPFN_MIX_ROW()
+  const float th = feat[(row_offset + r) * ldf + col];
+  if (logp_out != nullptr) {
+    const float lpf = bar_logp_row(p, nb, bz, ystats[1], ystats[0], th, red);
+    if (threadIdx.x == 0) logp_out[(row_offset + r) * ldo] = (lpf == -INFINITY) ? log_eps : lpf;
+  }
+  if (cdf_out != nullptr) {
+    const float c = bar_cdf_row(p, nb, bz, ystats[1], ystats[0], th, red);
+    if (threadIdx.x == 0) cdf_out[(row_offset + r) * ldo] = c;
+  }
+}
+
+// k_mix_score for repeated query rows: row r's mixture is p_rows[(row_offset + r) / per]
+// (k_mix_prob), loaded where k_mix_score leaves it -- the same outputs bit for bit.
+__global__ __launch_bounds__(256) void k_group_score(const float* __restrict__ p_rows, int64_t per, int nb,
+                                                     const float* __restrict__ bz, const float* __restrict__ ystats,
+                                                     int64_t row_offset, const float* __restrict__ feat, int64_t ldf,
+                                                     int col, float* __restrict__ logp_out,
+                                                     float* __restrict__ cdf_out, int64_t ldo, float log_eps) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* p = reinterpret_cast<float*>(smem + 64);
+  float* red = reinterpret_cast<float*>(smem);
+  const int64_t r = blockIdx.x;
+  const float* src = p_rows + ((row_offset + r) / per) * (int64_t)nb;
+  for (int b = threadIdx.x; b < nb; b += 256) p[b] = src[b];
+  __syncthreads();
+  const float th = feat[(row_offset + r) * ldf + col];
+  if (logp_out != nullptr) {
+    const float lpf = bar_logp_row(p, nb, bz, ystats[1], ystats[0], th, red);
+    if (threadIdx.x == 0) logp_out[(row_offset + r) * ldo] = (lpf == -INFINITY) ? log_eps : lpf;
+  }
+  if (cdf_out != nullptr) {
+    const float c = bar_cdf_row(p, nb, bz, ystats[1], ystats[0], th, red);
+    if (threadIdx.x == 0) cdf_out[(row_offset + r) * ldo] = c;
+  }
+}
+
+// Generic criterion.cdf(logits, y): softmax(logits row) -> the masses either side of y's bar
+// straight from the logits (no LDS beyond the reduction scratch) -> bar_cdf_finish.
+__global__ __launch_bounds__(256) void k_bar_cdf(const float* __restrict__ logits, const float* __restrict__ b,
+                                                 const float* __restrict__ y, int64_t R, int nb,
+                                                 float* __restrict__ out) {
+  __shared__ float red[4];
+  const int64_t r = blockIdx.x;
+  const float* lg = logits + r * nb;
+  const float th = y[r];
+  float mx = -INFINITY;
+  for (int k = threadIdx.x; k < nb; k += 256) mx = fmaxf(mx, lg[k]);
+  mx = block_reduce_max(mx, red);
+  const int j = bar_cdf_bucket(b, 1.0f, 0.0f, nb, th);
+  float sl = 0.f, sr = 0.f;
+  for (int k = threadIdx.x; k < nb; k += 256) {
+    const float v = __expf(lg[k] - mx);
+    if (k < j) sl += v;
+    if (k > j) sr += v;
+  }
+  sl = block_reduce_sum(sl, red);
+  sr = block_reduce_sum(sr, red);
+  if (threadIdx.x == 0) out[r] = bar_cdf_finish(sl, __expf(lg[j] - mx), sr, j, nb, b, 1.0f, 0.0f, th);
+}
+
 // Generic criterion.sample(logits): softmax(logits row) -> inverse CDF.
 __global__ __launch_bounds__(256) void k_bar_sample(const float* __restrict__ logits, const float* __restrict__ borders,
                                                     int64_t R, int nb, uint64_t seed, uint64_t counter,
@@ -3667,6 +3804,25 @@ void launch_mix_nll(const logit_t* logits, int64_t R, int E, int nb, float invT,
   if (R <= 0) return;
   NPFN_MIX_LAUNCH(k_mix_nll, nb, tr, s, logits, R, E, nb, invT, tr, bz, ystats, row_offset, feat, ldf, col, logp_acc,
                   log_eps);
+}
+void launch_group_score(const float* p_rows, int64_t per, int64_t R, int nb, const float* bz, const float* ystats,
+                        int64_t row_offset, const float* feat, int64_t ldf, int col, float* logp_out, float* cdf_out,
+                        int64_t ldo, float log_eps, hipStream_t s) {
+  if (R <= 0) return;
+  hipLaunchKernelGGL(k_group_score, dim3((unsigned)R), dim3(256), 64 + (size_t)nb * 4, s, p_rows, per, nb, bz, ystats,
+                     row_offset, feat, ldf, col, logp_out, cdf_out, ldo, log_eps);
+}
+void launch_mix_score(const logit_t* logits, int64_t R, int E, int nb, float invT, const MixTrans& tr, const float* bz,
+                      const float* ystats, int64_t row_offset, const float* feat, int64_t ldf, int col,
+                      float* logp_out, float* cdf_out, int64_t ldo, float log_eps, hipStream_t s) {
+  if (R <= 0) return;
+  NPFN_MIX_LAUNCH(k_mix_score, nb, tr, s, logits, R, E, nb, invT, tr, bz, ystats, row_offset, feat, ldf, col, logp_out,
+                  cdf_out, ldo, log_eps);
+}
+void launch_bar_cdf(const float* logits, const float* borders, const float* y, int64_t R, int nb, float* out,
+                    hipStream_t s) {
+  if (R <= 0) return;
+  hipLaunchKernelGGL(k_bar_cdf, dim3((unsigned)R), dim3(256), 0, s, logits, borders, y, R, nb, out);
 }
 void launch_mix_log_rows(const logit_t* logits, int64_t ld_rows, int64_t row0, int64_t R, int E, int nb, float invT,
                          const MixTrans& tr, float* out, int64_t ldo, hipStream_t s) {

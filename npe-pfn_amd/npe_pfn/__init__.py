@@ -7,6 +7,7 @@ this directory (``npe-pfn_amd``) on ``sys.path``.  The TabPFN forward runs in
 the HIP engine ``npe_pfn/_lib/libnpfn.so`` (C-ABI: include/npfn.h).
 """
 
+from npe_pfn.diagnostics import bar_cdf, pit_ks_statistic
 from npe_pfn.npe_pfn import NPE_PFN_Core, TabPFN_Based_NPE_PFN, TabPFN_Based_Uncond_Estimator
 from npe_pfn.restricted_prior import NPE_PFN_RestrictedPrior
 from npe_pfn.tsnpe_pfn import run_tsnpe_pfn
@@ -16,5 +17,7 @@ __all__ = [
     "NPE_PFN_RestrictedPrior",
     "TabPFN_Based_NPE_PFN",
     "TabPFN_Based_Uncond_Estimator",
+    "bar_cdf",
+    "pit_ks_statistic",
     "run_tsnpe_pfn",
 ]

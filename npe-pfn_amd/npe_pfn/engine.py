@@ -86,6 +86,7 @@ SIGNATURES = {
     "npfn_get_borders": (ctypes.c_int, [_vp, _vp, _vp]),
     "npfn_bar_sample": (ctypes.c_int, [_vp, _vp, _i64, _i32, _u64, _u64, _vp, _vp]),
     "npfn_bar_nll": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp]),
+    "npfn_bar_cdf": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp]),
     "npfn_bar_stats": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
     "npfn_predict_stats": (ctypes.c_int, [_vp, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp]),
     "npfn_ar_sample": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _u64, _i64, _vp, _vp, _f, _vp]),
@@ -93,6 +94,7 @@ SIGNATURES = {
                                                _f, _vp]),
     "npfn_ar_log_prob": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _f, _vp]),
     "npfn_ar_log_prob_repeated": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _f, _vp]),
+    "npfn_ar_score": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _f, _vp]),
     "npfn_box_support": (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     "npfn_compact_rows": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     "npfn_box_propose": (ctypes.c_int, [_vp, _vp, _i32, _i64, _u64, _u64, _i64, _vp, _vp]),
@@ -353,6 +355,20 @@ class Engine:
                                                logits.shape[1], _ptr(out), self.stream), "npfn_bar_nll")
         return out
 
+    def bar_cdf(self, logits: torch.Tensor, borders: torch.Tensor, y) -> torch.Tensor:
+        """npfn_bar_cdf: F(y_i) of the full-support bar distribution of each row of ``logits``
+        [N, n_bars] (half-normal tail bars, the density of :meth:`bar_nll`), [N] on the device."""
+        logits = _dev_f32(logits, self.device)
+        borders = _dev_f32(borders, self.device)
+        y = _dev_f32(y, self.device).reshape(-1)
+        if logits.ndim != 2 or borders.shape != (logits.shape[1] + 1,) or y.shape[0] != logits.shape[0]:
+            raise ValueError(f"bar_cdf: logits {tuple(logits.shape)}, borders {tuple(borders.shape)} and y "
+                             f"{tuple(y.shape)} do not match")
+        out = torch.empty(logits.shape[0], dtype=torch.float32, device=self.device)
+        _check(self.lib, self.lib.npfn_bar_cdf(_ptr(logits), _ptr(borders), _ptr(y), logits.shape[0],
+                                               logits.shape[1], _ptr(out), self.stream), "npfn_bar_cdf")
+        return out
+
     def _stats_buffers(self, n_rows: int, quantiles, mean: bool, mode: bool):
         qs = check_quantiles(quantiles)
         q = torch.tensor(qs, dtype=torch.float32).to(self.device) if qs else None
@@ -468,6 +484,40 @@ class Engine:
                    "npfn_ar_log_prob")
         self.n_features = dx + dth - 1
         return out
+
+    def ar_score(self, x_ctx, theta_ctx, x_unique, theta, eps: float = 1e-15, want_logp: bool = True,
+                 want_cdf: bool = True) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+        """npfn_ar_score: the teacher-forced pass of :meth:`ar_log_prob` with its per-step results
+        kept -- ``(logp_steps, cdf_steps)``, each [N, dim_theta] on the device or None when not
+        asked for.  Row i of ``theta`` [N, dim_theta] is scored under ``x_unique[i // (N // U)]``
+        (U = N: one query row per theta row; U < N: obs-major repeats, step 0 once per distinct
+        row).  ``logp_steps`` summed over its columns in order is :meth:`ar_log_prob`, bit for
+        bit; ``cdf_steps[:, k]`` is the PIT value F_k(theta_k | x, theta_<k)."""
+        if not (want_logp or want_cdf):
+            raise ValueError("ar_score: nothing asked for (want_logp and want_cdf are both False)")
+        self.full_range()
+        x_ctx = _dev_f32(x_ctx, self.device)
+        theta_ctx = _dev_f32(theta_ctx, self.device)
+        x_unique = _dev_f32(x_unique, self.device)
+        theta = _dev_f32(theta, self.device)
+        if x_ctx.ndim != 2 or theta_ctx.ndim != 2 or theta_ctx.shape[0] != x_ctx.shape[0]:
+            raise ValueError(f"ar_score: x_ctx {tuple(x_ctx.shape)} and theta_ctx {tuple(theta_ctx.shape)} do not match")
+        n, dx = x_ctx.shape
+        dth = theta_ctx.shape[1]
+        if theta.ndim != 2 or theta.shape[1] != dth:
+            raise ValueError(f"ar_score: theta {tuple(theta.shape)} is not [N, {dth}]")
+        N = theta.shape[0]
+        U = x_unique.shape[0] if x_unique.ndim == 2 else 0
+        if x_unique.ndim != 2 or x_unique.shape[1] != dx or U < 1 or N % U:
+            raise ValueError(f"ar_score: x_unique {tuple(x_unique.shape)} does not repeat into {N} rows of {dx}")
+        self.check_table(n, dx + dth - 1)
+        lp = torch.empty((N, dth), dtype=torch.float32, device=self.device) if want_logp else None
+        cdf = torch.empty((N, dth), dtype=torch.float32, device=self.device) if want_cdf else None
+        _check(self.lib, self.lib.npfn_ar_score(self.h, _ptr(x_ctx), _ptr(theta_ctx), n, dx, dth, _ptr(x_unique), U,
+                                                _ptr(theta), N, _ptr(lp), _ptr(cdf), float(eps), self.stream),
+               "npfn_ar_score")
+        self.n_features = dx + dth - 1
+        return lp, cdf
 
     # ------------------------------------------------------- support kernels
     def box_support(self, theta: torch.Tensor, low: torch.Tensor, high: torch.Tensor) -> torch.Tensor:

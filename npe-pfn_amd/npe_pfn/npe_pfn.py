@@ -29,6 +29,7 @@ from torch import Tensor
 from torch.distributions import Distribution
 
 from .accept_reject_sampler import accept_reject_sample
+from .diagnostics import bar_cdf
 from .kmeans import KMeansState
 from .support_posterior import (get_filtering_method, latest_filtering, no_filtering,
                                 standardized_euclidean_filtering)
@@ -304,8 +305,73 @@ class NPE_PFN_Core:
                                                                                      **ratio_kwargs).cpu()
         return out
 
-    def log_prob_batched(self, theta: Tensor, x: Tensor):
-        raise NotImplementedError
+    def log_prob_batched(self, theta: Tensor, x: Tensor, eps: float = 1e-15, return_steps: bool = False):
+        """Autoregressive log q(theta_m | x_m) of many (theta, x) pairs in one teacher-forced pass
+        (the reference declares this method and leaves it unimplemented, :457-460).
+
+        ``x`` [M, dx]; ``theta`` [M, d_theta] gives [M], ``theta`` [M, K, d_theta] (K thetas per
+        observation) gives [M, K].  The context is the full table, as in ``sample_batched`` (no
+        per-observation filter), so every autoregressive step is fitted once for all pairs.
+        ``return_steps=True`` also returns the per-dimension log densities [..., d_theta], whose
+        sum over the last axis (in order) is the first result.  On the device of ``x``."""
+        lp, steps, _ = self._score_batched(theta, x, eps, want_logp=True, want_cdf=False)
+        return (lp, steps) if return_steps else lp
+
+    def pit_batched(self, theta: Tensor, x: Tensor) -> Tensor:
+        """Per-dimension probability integral transform u_k = F_k(theta_k | x, theta_<k) of the
+        pairs of :meth:`log_prob_batched` (same shapes): [..., d_theta].  Uniform on [0, 1] in
+        dimension k exactly when conditional k is calibrated on the true pairs
+        (:func:`npe_pfn.diagnostics.pit_ks_statistic`); needs no posterior samples."""
+        return self._score_batched(theta, x, 1e-15, want_logp=False, want_cdf=True)[2]
+
+    def _score_batched(self, theta: Tensor, x: Tensor, eps: float, want_logp: bool, want_cdf: bool):
+        """(summed log density [...], per-step log densities [..., d_theta], PIT [..., d_theta]) of
+        one teacher-forced pass over the full table; entries not asked for are None."""
+        x = self._validate_x(self._embed(x) if self.embedding_net else x)
+        theta = torch.as_tensor(theta)
+        if theta.ndim not in (2, 3):
+            raise ValueError(f"theta must be [M, d_theta] or [M, K, d_theta], got shape {tuple(theta.shape)}")
+        n_obs, dth = x.shape[0], self._theta_train.shape[1]
+        if theta.shape[0] != n_obs:
+            raise ValueError(f"theta has {theta.shape[0]} observations, x has {n_obs}")
+        if theta.shape[-1] != dth:
+            raise ValueError(f"theta has {theta.shape[-1]} dimensions, the training data {dth}")
+        lead = theta.shape[:-1]
+        flat = theta.reshape(-1, dth)
+        with self._reuse_fits():
+            if hasattr(self._model, "ar_score"):
+                steps, pit = self._model.ar_score(self._x_train, self._theta_train, x, flat, eps=eps,
+                                                  want_logp=want_logp, want_cdf=want_cdf)
+            else:
+                x_query = x if theta.ndim == 2 else x.repeat_interleave(theta.shape[1], dim=0)
+                steps, pit = self._score_generic(x_query, flat, eps, want_logp, want_cdf)
+        lp = None
+        if want_logp:
+            lp = torch.zeros(flat.shape[0], dtype=steps.dtype, device=steps.device)
+            for k in range(dth):   # in order: the engine's own summation of ar_log_prob
+                lp += steps[:, k]
+            lp = lp.reshape(lead).to(x.device)
+            steps = steps.reshape(*lead, dth).to(x.device)
+        if want_cdf:
+            pit = pit.reshape(*lead, dth).to(x.device)
+        return lp, steps, pit
+
+    def _score_generic(self, x_query: Tensor, theta: Tensor, eps: float, want_logp: bool, want_cdf: bool):
+        """The dimension loop of :meth:`_autoregressive_log_prob` through the tabpfn surface, with
+        every step's log density and CDF (:func:`npe_pfn.diagnostics.bar_cdf`) kept."""
+        joint = torch.cat([self._x_train, self._theta_train], dim=1)
+        test = torch.cat([x_query, theta], dim=1)
+        dx = self._x_train.shape[1]
+        steps, pit = [], []
+        for k in range(theta.shape[1]):
+            self._model.fit(joint[:, : dx + k], joint[:, dx + k])
+            pred = self._model.predict(test[:, : dx + k], output_type="full", quantiles=[])
+            if want_logp:
+                step = -pred["criterion"](pred["logits"], test[:, dx + k])
+                steps.append(torch.where(step == float("-inf"), torch.log(torch.tensor(eps)).to(step), step))
+            if want_cdf:
+                pit.append(bar_cdf(pred["logits"], pred["criterion"].borders, test[:, dx + k]))
+        return (torch.stack(steps, 1) if want_logp else None), (torch.stack(pit, 1) if want_cdf else None)
 
     def _autoregressive_log_prob(self, theta: Tensor, x: Tensor = None, repeat_x: bool = True,
                                  eps: float = 1e-15) -> Tensor:
@@ -582,6 +648,17 @@ class TabPFN_Based_Uncond_Estimator(NPE_PFN_Core):
             log_probs = torch.cat(lps, dim=0)
             return samples, log_probs[perm.to(log_probs.device)].to(out_device)
         return samples
+
+    def log_prob_batched(self, theta: Tensor, x: Tensor = None, eps: float = 1e-15, return_steps: bool = False):
+        """Not provided: this estimator's ``x`` is a dummy column, so there are no (theta, x) pairs
+        to score together; use :meth:`log_prob`."""
+        raise NotImplementedError("TabPFN_Based_Uncond_Estimator has no observations to batch over (its x is a "
+                                  "dummy column); use log_prob(theta)")
+
+    def pit_batched(self, theta: Tensor, x: Tensor = None) -> Tensor:
+        """Not provided, for the reason given at :meth:`log_prob_batched`."""
+        raise NotImplementedError("TabPFN_Based_Uncond_Estimator has no observations to batch over (its x is a "
+                                  "dummy column)")
 
     def log_prob(self, theta: Tensor, x: Tensor = None, max_sampling_batch_size: int = 10_000,
                  mode: str = "autoregressive", eps: float = 1e-15, **ratio_kwargs) -> Tensor:

@@ -12,8 +12,8 @@ uses exactly this surface of it:
 
 :class:`TabPFNRegressor` provides that surface over ``libnpfn.so`` and, in
 addition, the fused autoregressive entry points (``ar_sample``,
-``ar_log_prob``) that :class:`npe_pfn.npe_pfn.NPE_PFN_Core` uses when its
-estimator offers them.
+``ar_log_prob``, ``ar_score``) that :class:`npe_pfn.npe_pfn.NPE_PFN_Core` uses
+when its estimator offers them.
 
 Sampling randomness: tabpfn draws ``criterion.sample`` uniforms from torch's
 global RNG [ext]; here they come from Philox4x32-10 keyed by
@@ -281,6 +281,13 @@ class TabPFNRegressor:
         _check_table(len(x_ctx), x_ctx.shape[1] + theta_ctx.shape[1] - 1, self.ignore_pretraining_limits)
         return self.engine.ar_log_prob(x_ctx, theta_ctx, x_query, theta, eps, x_unique=x_unique)
 
+    def ar_score(self, x_ctx, theta_ctx, x_unique, theta, eps: float = 1e-15, want_logp: bool = True,
+                 want_cdf: bool = True):
+        """Per-dimension log densities and PIT values of the teacher-forced pass (Engine.ar_score):
+        ``(logp_steps, cdf_steps)``, each [N, dim_theta] on the device or None."""
+        _check_table(len(x_ctx), x_ctx.shape[1] + theta_ctx.shape[1] - 1, self.ignore_pretraining_limits)
+        return self.engine.ar_score(x_ctx, theta_ctx, x_unique, theta, eps, want_logp=want_logp, want_cdf=want_cdf)
+
     @contextlib.contextmanager
     def reuse_fits(self):
         """Within the block, ar_sample / ar_log_prob calls share their per-step fits (one fresh
@@ -340,6 +347,14 @@ class BarCriterion:
                                device=torch.as_tensor(logits).device)
         q = self._stats(logits, levels)["quantiles"]
         return q[0] if lp.ndim == 0 else q
+
+    def cdf(self, logits: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        """F(y) per row under the density of :meth:`__call__` (half-normal tail bars), returned on
+        the device of ``y``.  ``icdf(cdf(y)) == y`` holds on the inner bars only: ``icdf`` and
+        ``sample`` interpolate linearly inside the two tail bars, as tabpfn's do."""
+        y = torch.as_tensor(y)
+        out = self._reg.engine.bar_cdf(logits, self.borders, y)
+        return out.to(y.device)
 
     def __call__(self, logits: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         """NLL per row, returned on the device of ``y``."""
