@@ -244,6 +244,39 @@ int npfn_ar_sample_repeated(npfn_engine* h, const float* x_ctx, const float* the
                             int64_t n_rows, uint64_t counter, int64_t row_base, float* theta_out,
                             float* log_prob_out, float eps, void* stream);
 
+/* npfn_ar_sample_repeated that also returns the posterior marginals averaged over the sampler's
+ * own conditionals ("Rao-Blackwellised" marginals).  Same arguments, fits, fit reuse
+ * (npfn_set_fit_token), side-stream prefit, chunking (npfn_set_chunk_rows) and step 0 once per
+ * distinct row; theta_out / log_prob_out (either may be NULL) are bit for bit those of
+ * npfn_ar_sample_repeated.  With per = n_rows / n_unique and p_i the ensemble mixture row i
+ * draws theta_k from at step k (given x and the row's own theta_<k):
+ *  - marg_out [n_unique, dim_theta, n_bars]: [u, k, b] = (1 / per) * sum over the per rows i of
+ *    observation u of p_i[b] / sum_b p_i[b] -- the estimate of the marginal bar masses of
+ *    q(theta_k | x_u) that integrates each conditional instead of sampling it.  Every [u, k]
+ *    row sums to 1 (to fp32 rounding).  At step 0 all rows of an observation share one mixture,
+ *    so [u, 0] is that mixture normalised, with no averaging;
+ *  - borders_out [dim_theta, n_bars + 1]: [k] = step k's bar borders, what npfn_get_borders
+ *    returns after that step's fit, bit for bit.  All rows of a step share them, which is why
+ *    the average over draws is a plain column sum with no re-binning.
+ * Row k of marg_out with row k of borders_out is a bar distribution like any other:
+ * npfn_bar_stats / npfn_bar_cdf / npfn_bar_nll on log(marg_out[u, k]) summarise it.
+ * Reduction: per row 1 / sum_b p in fp64; rows added in row order in fp64 within strips of 64
+ * consecutive rows of an observation, the strips added in order, one division by per, one
+ * rounding to fp32.  No atomics; the summation order does not depend on the chunking, so the
+ * result is bitwise reproducible and independent of npfn_set_chunk_rows, and an observation's
+ * marginals do not depend on which other observations share the call (given the same row_base
+ * for its rows).  A row whose mixture has no mass makes its observation's marginal NaN.
+ * Device memory: a [min(chunk rows, n_rows), n_bars] fp32 window (328 MB at 16384 x 5000) and
+ * [n_unique * ceil(per / 64), n_bars] fp64 partials.  Asynchronous.
+ * Errors: NPFN_EINVAL for n_unique < 1, n_rows < n_unique, n_unique not dividing n_rows, NULL
+ * marg_out or borders_out (these four are checked first, on the host, before the engine is
+ * touched), and whatever npfn_ar_sample_repeated rejects; NPFN_ESTATE on a partial estimator
+ * range. */
+int npfn_ar_marginals(npfn_engine* h, const float* x_ctx, const float* theta_ctx, int64_t n_ctx,
+                      int32_t dim_x, int32_t dim_theta, const float* x_unique, int64_t n_unique,
+                      int64_t n_rows, uint64_t counter, int64_t row_base, float* theta_out,
+                      float* log_prob_out, float eps, float* marg_out, float* borders_out, void* stream);
+
 /* Teacher-forced autoregressive log density (npe_pfn.py:462-524):
  * log_prob_out [n_rows] = sum_k -NLL_k(theta[:, k] | x, theta[:, :k]). */
 int npfn_ar_log_prob(npfn_engine* h, const float* x_ctx, const float* theta_ctx, int64_t n_ctx,

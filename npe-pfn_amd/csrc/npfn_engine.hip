@@ -181,6 +181,9 @@ struct npfn_engine {
   DevBuf dh, logits, tgt;
   DevBuf joint, feat, logp;
   DevBuf pu;  // [n_unique][nb] step-0 mixtures of npfn_ar_sample_repeated
+  // npfn_ar_marginals: [chunk rows][nb] row mixtures of a chunk, [rows] fp64 1 / row sums,
+  // [n_unique * strips][nb] fp64 strip partials of the step in flight
+  DevBuf margwin, marginv, margpart;
   DevBuf mixlog, borders;  // npfn_predict_stats: [kStatsRows][nb] mixture logits of a row window, [nb + 1] borders
   // npfn_predict_accept / npfn_restricted_box_round: [chunk rows][n_classes] probabilities of a
   // chunk; [n_rows][dim] proposals and [n_rows] accept flags of a round
@@ -1257,10 +1260,15 @@ int ar_step_fit(npfn_engine* h, const float* joint, int Ft, int64_t n, int dx, i
 // rows, step 0 -- whose features are the query rows alone -- runs the forward, decoder and
 // ensemble mix once per distinct row and every draw samples from its row's mixture
 // (k_group_sample); steps >= 1 see distinct sampled columns and run over every row.
+// npfn_ar_marginals (marg_out / borders_out set, n_unique >= 1): every step's row mixtures also
+// pass through the window margwin -- k_mix_prob writes a chunk's masses, k_group_sample with
+// per = 1 draws from them (k_mix_sample's draw, bit for bit) and launch_marg_accum adds them to
+// the observations' sums; step 0's marginal is the distinct row's own mixture.
 int ar_sample_impl(npfn_engine* h, const float* x_ctx, const float* theta_ctx, int64_t n_ctx, int dim_x,
                    int dim_theta, const float* x_query, int64_t n_unique, int64_t n_rows, uint64_t counter,
-                   int64_t row_base, float* theta_out, float* log_prob_out, float eps, hipStream_t s) {
-  if (!theta_out) return fail(NPFN_EINVAL, "ar_sample: null theta_out");
+                   int64_t row_base, float* theta_out, float* log_prob_out, float eps, hipStream_t s,
+                   float* marg_out = nullptr, float* borders_out = nullptr) {
+  if (!theta_out && !marg_out) return fail(NPFN_EINVAL, "ar_sample: null theta_out");
   if (row_base < 0) return fail(NPFN_EINVAL, "ar_sample: negative row_base");
   RCHK(need_full_range(h, "ar_sample"));
   RCHK(ensure_pipelines(h, false));
@@ -1273,12 +1281,19 @@ int ar_sample_impl(npfn_engine* h, const float* x_ctx, const float* theta_ctx, i
   float* feat = (float*)h->feat.p;
   float* logp = log_prob_out ? (float*)h->logp.p : nullptr;
   bool reuse = false, piped = false;
+  const int64_t win_rows = std::min(h->chunk_rows, n_rows);
+  if (marg_out) {
+    RCHK(ensure(h->margwin, (size_t)win_rows * nb * sizeof(float), s));
+    RCHK(ensure(h->marginv, (size_t)std::max(win_rows, n_unique) * sizeof(double), s));
+    RCHK(ensure(h->margpart, (size_t)n_unique * marg_strips(per) * nb * sizeof(double), s));
+  }
   begin_ar_fits(h, n_ctx, dim_x, dim_theta, reuse);
   if (!reuse) RCHK(ar_prefit(h, joint, Ft, n_ctx, dim_x, dim_theta, s, piped));
   for (int k = 0; k < dim_theta; ++k) {
     const int F = dim_x + k;
     h->f = step_fit(h, k);
     if (!reuse) RCHK(ar_step_fit(h, joint, Ft, n_ctx, dim_x, dim_theta, k, piped, s));
+    if (marg_out) launch_borders(h->bz, (const float*)h->f->ystats.p, nb, borders_out + (int64_t)k * (nb + 1), s);
     if (k == 0 && n_unique > 0 && n_rows > 0) {
       RCHK(ensure(h->pu, (size_t)n_unique * nb * sizeof(float), s));
       float* pu = (float*)h->pu.p;
@@ -1288,6 +1303,11 @@ int ar_sample_impl(npfn_engine* h, const float* x_ctx, const float* theta_ctx, i
         ProfGuard g(h, P_MIX_SAMPLE, 0.0, (double)E * rows * nb * sizeof(logit_t), s);
         launch_mix_prob((const logit_t*)h->logits.p, rows, E, nb, invT, h->mixtrans(), pu + u0 * nb, s);
       }
+      if (marg_out) {  // one mixture per observation: its normalised masses, no averaging
+        ProfGuard g(h, P_OTHER, 0.0, (double)n_unique * nb * 24, s);
+        launch_marg_accum(pu, 0, n_unique, 1, nb, (double*)h->marginv.p, (double*)h->margpart.p, s);
+        launch_marg_final((const double*)h->margpart.p, n_unique, 1, nb, marg_out, (int64_t)dim_theta * nb, s);
+      }
       ProfGuard g(h, P_MIX_SAMPLE, 0.0, (double)n_rows * nb * 4, s);
       launch_group_sample(pu, per, n_rows, nb, h->bz, (const float*)h->f->ystats.p, h->cfg.random_state,
                           counter + (uint64_t)k, 0, (uint64_t)row_base, feat, Ft, F, logp, log_eps, s);
@@ -1296,14 +1316,34 @@ int ar_sample_impl(npfn_engine* h, const float* x_ctx, const float* theta_ctx, i
     for (int64_t r0 = 0; r0 < n_rows; r0 += h->chunk_rows) {
       const int64_t rows = std::min(h->chunk_rows, n_rows - r0);
       RCHK(predict_logits_chunk(h, feat + r0 * Ft, Ft, rows, s));
+      if (marg_out) {
+        float* win = (float*)h->margwin.p;
+        {
+          ProfGuard g(h, P_MIX_SAMPLE, 0.0, (double)E * rows * nb * sizeof(logit_t) + (double)rows * nb * 8, s);
+          launch_mix_prob((const logit_t*)h->logits.p, rows, E, nb, invT, h->mixtrans(), win, s);
+          // k_group_sample reads the mixture of row row_offset + r at p_rows[(row_offset + r) / per]:
+          // with per = 1 and the base moved back by r0 rows that is window row r (the moved base is
+          // only ever indexed from row r0 on)
+          launch_group_sample(win - r0 * nb, 1, rows, nb, h->bz, (const float*)h->f->ystats.p, h->cfg.random_state,
+                              counter + (uint64_t)k, r0, (uint64_t)row_base, feat, Ft, F, logp, log_eps, s);
+        }
+        ProfGuard g(h, P_OTHER, 0.0, (double)rows * nb * 8, s);
+        launch_marg_accum(win, r0, rows, per, nb, (double*)h->marginv.p, (double*)h->margpart.p, s);
+        continue;
+      }
       ProfGuard g(h, P_MIX_SAMPLE, 0.0, (double)E * rows * nb * sizeof(logit_t), s);
       launch_mix_sample((const logit_t*)h->logits.p, rows, E, nb, invT, h->mixtrans(), h->bz, (const float*)h->f->ystats.p,
                         h->cfg.random_state, counter + (uint64_t)k, r0, (uint64_t)row_base, feat, Ft, F, logp,
                         log_eps, s);
     }
+    if (marg_out) {
+      ProfGuard g(h, P_OTHER, 0.0, (double)n_unique * marg_strips(per) * nb * 8, s);
+      launch_marg_final((const double*)h->margpart.p, n_unique, per, nb, marg_out + (int64_t)k * nb,
+                        (int64_t)dim_theta * nb, s);
+    }
   }
   end_ar_fits(h, n_ctx, dim_x, dim_theta);
-  launch_copy_cols(feat + dim_x, Ft, theta_out, dim_theta, n_rows, dim_theta, 0, s);
+  if (theta_out) launch_copy_cols(feat + dim_x, Ft, theta_out, dim_theta, n_rows, dim_theta, 0, s);
   if (log_prob_out && n_rows > 0)
     HIPCHK(hipMemcpyAsync(log_prob_out, h->logp.p, n_rows * sizeof(float), hipMemcpyDeviceToDevice, s));
   HIPCHK(hipGetLastError());
@@ -1533,7 +1573,7 @@ int npfn_engine_destroy(npfn_engine* h) {
   h->wmain.release();
   h->wside.release();
   DevBuf* bufs[] = {&h->dh,      &h->logits, &h->tgt,
-                    &h->joint, &h->feat,     &h->logp, &h->pu, &h->mixlog, &h->borders, &h->rp_probs, &h->rp_theta, &h->rp_mask, &h->views, &h->ftype, &h->ett,     &h->fp_salt};
+                    &h->joint, &h->feat,     &h->logp, &h->pu, &h->margwin, &h->marginv, &h->margpart, &h->mixlog, &h->borders, &h->rp_probs, &h->rp_theta, &h->rp_mask, &h->views, &h->ftype, &h->ett,     &h->fp_salt};
   for (DevBuf* b : bufs) free_buf(*b);
   delete h;
   return NPFN_OK;
@@ -1779,6 +1819,19 @@ int npfn_ar_sample_repeated(npfn_engine* h, const float* x_ctx, const float* the
     return fail(NPFN_EINVAL, "ar_sample_repeated: need n_unique >= 1 dividing n_rows");
   return ar_sample_impl(h, x_ctx, theta_ctx, n_ctx, dim_x, dim_theta, x_unique, n_unique, n_rows, counter, row_base,
                         theta_out, log_prob_out, eps, (hipStream_t)stream);
+}
+
+int npfn_ar_marginals(npfn_engine* h, const float* x_ctx, const float* theta_ctx, int64_t n_ctx, int32_t dim_x,
+                      int32_t dim_theta, const float* x_unique, int64_t n_unique, int64_t n_rows, uint64_t counter,
+                      int64_t row_base, float* theta_out, float* log_prob_out, float eps, float* marg_out,
+                      float* borders_out, void* stream) {
+  // host checks first: they answer without an engine or a device
+  if (n_unique < 1 || n_rows < n_unique || n_rows % n_unique != 0)
+    return fail(NPFN_EINVAL, "ar_marginals: need n_unique >= 1 dividing n_rows >= n_unique");
+  if (!marg_out || !borders_out) return fail(NPFN_EINVAL, "ar_marginals: null marg_out or borders_out");
+  RCHK(check_engine(h));
+  return ar_sample_impl(h, x_ctx, theta_ctx, n_ctx, dim_x, dim_theta, x_unique, n_unique, n_rows, counter, row_base,
+                        theta_out, log_prob_out, eps, (hipStream_t)stream, marg_out, borders_out);
 }
 
 int npfn_ar_log_prob(npfn_engine* h, const float* x_ctx, const float* theta_ctx, int64_t n_ctx, int32_t dim_x,

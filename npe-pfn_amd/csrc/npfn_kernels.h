@@ -310,6 +310,18 @@ void launch_bar_sample(const float* logits, const float* borders, int64_t R, int
 void launch_bar_nll(const float* logits, const float* borders, const float* y, int64_t R, int nb, float* out,
                     hipStream_t s);
 void launch_borders(const float* bz, const float* ystats, int nb, float* out, hipStream_t s);
+// npfn_ar_marginals: the mean of the normalised row mixtures per observation, from windows of
+// launch_mix_prob's masses.  Window row r (of `rows`) is row r0 + r of the call and belongs to
+// observation (r0 + r) / per.  launch_marg_accum adds a window into part
+// [n_unique * marg_strips(per)][nb] (fp64 strip partials; inv [rows] is scratch); the windows of
+// a step must arrive in row order, every row once.  launch_marg_final then writes
+// out[u * ldo + b] = the mean of observation u.  Fixed summation order, independent of how the
+// rows were cut into windows; no atomics.
+int64_t marg_strips(int64_t per);
+void launch_marg_accum(const float* win, int64_t r0, int64_t rows, int64_t per, int nb, double* inv, double* part,
+                       hipStream_t s);
+void launch_marg_final(const double* part, int64_t n_unique, int64_t per, int nb, float* out, int64_t ldo,
+                       hipStream_t s);
 // dst[r][dst_col0 + c] = src[r / per][c] (per = 1: a plain column copy; per > 1: rows repeated
 // obs-major, as x.repeat_interleave(per, 0))
 void launch_copy_cols(const float* src, int64_t lds, float* dst, int64_t ldd, int64_t rows, int cols,

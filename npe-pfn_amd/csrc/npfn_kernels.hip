@@ -3381,6 +3381,84 @@ __global__ void k_borders(const float* __restrict__ bz, const float* __restrict_
   if (i <= nb) out[i] = bz[i] * ystats[1] + ystats[0];
 }
 
+// ======================================================= marginals (npfn_ar_marginals)
+// The mean over an observation's rows of the normalised row mixtures p_row / sum_b p_row, from a
+// window win [rows][nb] of k_mix_prob's masses (window row r = row r0 + r of the call, which
+// belongs to observation (r0 + r) / per).  Three streaming kernels, no floating-point atomics and
+// one summation order whatever the chunking:
+//  * k_marg_rowinv: inv[r] = 1 / sum_b win[r][b] in fp64 (strided partial per thread, then a
+//    fixed LDS tree);
+//  * k_marg_accum: an observation's rows are cut into strips of kMargStrip consecutive rows,
+//    counted from the observation's first row; one thread owns column b of a strip and adds the
+//    strip's rows of this window in row order into part[strip][b] (fp64).  A strip that began in
+//    an earlier window continues from its stored partial, so the chain of additions is the same
+//    however the rows were cut into windows;
+//  * k_marg_final: out[u][b] = (sum of the observation's strip partials, in strip order) / per,
+//    rounded to fp32 once.
+// The strips are what makes the grid wide with one observation: 10 000 rows x 5000 bars is
+// 157 strips x 20 column tiles = 3140 blocks of coalesced 1 KB row segments, not 5000 threads
+// walking 10 000 rows each.
+constexpr int kMargStrip = 64;
+
+__global__ __launch_bounds__(256) void k_marg_rowinv(const float* __restrict__ win, int nb, double* __restrict__ inv) {
+  __shared__ double sh[256];
+  const float* row = win + (int64_t)blockIdx.x * nb;
+  double acc = 0.0;
+  for (int b = threadIdx.x; b < nb; b += 256) acc += (double)row[b];
+  sh[threadIdx.x] = acc;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) inv[blockIdx.x] = 1.0 / sh[0];
+}
+
+// grid (strips touched by the window, column tiles): strip sid0 + blockIdx.x, of observation
+// sid / S (S = strips per observation)
+__global__ __launch_bounds__(256) void k_marg_accum(const float* __restrict__ win, const double* __restrict__ inv,
+                                                    int64_t r0, int64_t rows, int64_t per, int64_t S, int64_t sid0,
+                                                    int nb, double* __restrict__ part) {
+  const int col = blockIdx.y * 256 + threadIdx.x;
+  if (col >= nb) return;
+  const int64_t sid = sid0 + blockIdx.x, u = sid / S, j = sid - u * S;
+  const int64_t g0 = u * per + j * kMargStrip;
+  const int64_t e1 = (j + 1) * kMargStrip, g1 = u * per + (e1 < per ? e1 : per);
+  const int64_t lo = g0 > r0 ? g0 : r0, hi = g1 < r0 + rows ? g1 : r0 + rows;
+  double* dst = part + sid * nb + col;
+  double acc = lo == g0 ? 0.0 : *dst;   // the strip's first row is in this window: a fresh sum
+  const float* src = win + (lo - r0) * nb + col;
+  const double* iv = inv + (lo - r0);
+  // eight rows' loads in flight, added in row order; an explicit fma in both loops, so that the
+  // rounding of a row's term does not depend on which loop it falls into
+  const int64_t n = hi - lo;
+  int64_t i = 0;
+  for (; i + 8 <= n; i += 8) {
+    float v[8];
+    double w[8];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+      v[t] = src[(i + t) * nb];
+      w[t] = iv[i + t];
+    }
+#pragma unroll
+    for (int t = 0; t < 8; ++t) acc = fma((double)v[t], w[t], acc);
+  }
+  for (; i < n; ++i) acc = fma((double)src[i * nb], iv[i], acc);
+  if (n > 0) *dst = acc;
+}
+
+// grid (observations, column tiles)
+__global__ __launch_bounds__(256) void k_marg_final(const double* __restrict__ part, int64_t S, int nb, int64_t per,
+                                                    float* __restrict__ out, int64_t ldo) {
+  const int col = blockIdx.y * 256 + threadIdx.x;
+  if (col >= nb) return;
+  const int64_t u = blockIdx.x;
+  double acc = 0.0;
+  for (int64_t j = 0; j < S; ++j) acc += part[(u * S + j) * nb + col];
+  out[u * ldo + col] = (float)(acc / (double)per);
+}
+
 // ======================================================= small utilities
 __global__ void k_copy_cols(const float* __restrict__ src, int64_t lds, float* __restrict__ dst,
                             int64_t ldd, int64_t rows, int cols, int dst_col0, int64_t per) {
@@ -3846,6 +3924,23 @@ void launch_bar_nll(const float* logits, const float* borders, const float* y, i
 }
 void launch_borders(const float* bz, const float* ystats, int nb, float* out, hipStream_t s) {
   hipLaunchKernelGGL(k_borders, dim3(blocks_for(nb + 1, 256)), dim3(256), 0, s, bz, ystats, nb, out);
+}
+int64_t marg_strips(int64_t per) { return (per + kMargStrip - 1) / kMargStrip; }
+void launch_marg_accum(const float* win, int64_t r0, int64_t rows, int64_t per, int nb, double* inv, double* part,
+                       hipStream_t s) {
+  if (rows <= 0) return;
+  const int64_t S = marg_strips(per);
+  auto strip_of = [&](int64_t g) { return (g / per) * S + (g % per) / kMargStrip; };
+  const int64_t sid0 = strip_of(r0), n_strips = strip_of(r0 + rows - 1) - sid0 + 1;
+  hipLaunchKernelGGL(k_marg_rowinv, dim3((unsigned)rows), dim3(256), 0, s, win, nb, inv);
+  hipLaunchKernelGGL(k_marg_accum, dim3((unsigned)n_strips, blocks_for(nb, 256)), dim3(256), 0, s, win, inv, r0, rows,
+                     per, S, sid0, nb, part);
+}
+void launch_marg_final(const double* part, int64_t n_unique, int64_t per, int nb, float* out, int64_t ldo,
+                       hipStream_t s) {
+  if (n_unique <= 0) return;
+  hipLaunchKernelGGL(k_marg_final, dim3((unsigned)n_unique, blocks_for(nb, 256)), dim3(256), 0, s, part,
+                     marg_strips(per), nb, per, out, ldo);
 }
 void launch_copy_cols(const float* src, int64_t lds, float* dst, int64_t ldd, int64_t rows, int cols,
                       int dst_col0, hipStream_t s, int64_t per) {

@@ -8,6 +8,7 @@ the HIP engine ``npe_pfn/_lib/libnpfn.so`` (C-ABI: include/npfn.h).
 """
 
 from npe_pfn.diagnostics import bar_cdf, pit_ks_statistic
+from npe_pfn.marginals import PosteriorMarginals
 from npe_pfn.npe_pfn import NPE_PFN_Core, TabPFN_Based_NPE_PFN, TabPFN_Based_Uncond_Estimator
 from npe_pfn.restricted_prior import NPE_PFN_RestrictedPrior
 from npe_pfn.tsnpe_pfn import run_tsnpe_pfn
@@ -15,6 +16,7 @@ from npe_pfn.tsnpe_pfn import run_tsnpe_pfn
 __all__ = [
     "NPE_PFN_Core",
     "NPE_PFN_RestrictedPrior",
+    "PosteriorMarginals",
     "TabPFN_Based_NPE_PFN",
     "TabPFN_Based_Uncond_Estimator",
     "bar_cdf",

@@ -410,6 +410,18 @@ def sample_batched_sharded(posterior, x: Tensor, sample_shape=torch.Size(), with
     return th
 
 
+def marginals_single_rank(posterior, x: Tensor, group=None, **kwargs):
+    """``posterior.marginals(x, ...)`` inside a process group of ONE rank.  The call is not
+    sharded: with more ranks every rank would form its own average over its own draws, and
+    combining them needs a weighted reduction of the per-rank marginals that is not provided."""
+    _, world = _rank_world(group)
+    if world > 1:
+        raise NotImplementedError(f"marginals is single-GPU: the process group has {world} ranks; call "
+                                  "posterior.marginals(x) on one rank (multi-GPU sharding of the call is not "
+                                  "provided)")
+    return posterior.marginals(x, **kwargs)
+
+
 def sample_replicas(posterior, x: Tensor, n: int, group=None, **kwargs) -> Tensor:
     """Weak-scaling replicas: every rank draws ``n`` samples of the same observation; ``[world*n, dθ]``."""
     s = posterior.sample((n,), x=x, **kwargs)

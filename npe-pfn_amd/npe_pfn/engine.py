@@ -92,6 +92,8 @@ SIGNATURES = {
     "npfn_ar_sample": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _u64, _i64, _vp, _vp, _f, _vp]),
     "npfn_ar_sample_repeated": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _i64, _u64, _i64, _vp, _vp,
                                                _f, _vp]),
+    "npfn_ar_marginals": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _i64, _u64, _i64, _vp, _vp, _f,
+                                         _vp, _vp, _vp]),
     "npfn_ar_log_prob": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _f, _vp]),
     "npfn_ar_log_prob_repeated": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _f, _vp]),
     "npfn_ar_score": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _f, _vp]),
@@ -453,6 +455,40 @@ class Engine:
                    "npfn_ar_sample")
         self.n_features = dx + dth - 1
         return theta, lp
+
+    def ar_marginals(self, x_ctx, theta_ctx, x_unique, n_rows: int, counter: int, with_log_prob: bool = False,
+                     eps: float = 1e-15, row_base: int = 0):
+        """npfn_ar_marginals: :meth:`ar_sample` over ``x_unique.repeat_interleave(n_rows // U, 0)``
+        that also averages, per observation and step, the mixtures the draws were taken from.
+        Returns ``(theta [n_rows, dim_theta], log_prob [n_rows] or None, probs [U, dim_theta,
+        n_bars], borders [dim_theta, n_bars + 1])`` on the device; ``theta`` and ``log_prob`` are
+        bit for bit those of :meth:`ar_sample` with the same counter and row_base.
+        ``probs[u, k]`` are the bar masses of the marginal of theta_k given ``x_unique[u]`` on
+        ``borders[k]``: the mean over the observation's draws of their conditionals."""
+        self.full_range()
+        x_ctx = _dev_f32(x_ctx, self.device)
+        theta_ctx = _dev_f32(theta_ctx, self.device)
+        x_unique = _dev_f32(x_unique, self.device)
+        if x_ctx.ndim != 2 or theta_ctx.ndim != 2 or theta_ctx.shape[0] != x_ctx.shape[0]:
+            raise ValueError(f"ar_marginals: x_ctx {tuple(x_ctx.shape)} and theta_ctx {tuple(theta_ctx.shape)} do "
+                             "not match")
+        n, dx = x_ctx.shape
+        dth = theta_ctx.shape[1]
+        N = int(n_rows)
+        U = x_unique.shape[0] if x_unique.ndim == 2 else 0
+        if x_unique.ndim != 2 or x_unique.shape[1] != dx or U < 1 or N < U or N % U:
+            raise ValueError(f"ar_marginals: x_unique {tuple(x_unique.shape)} does not repeat into {N} rows of {dx}")
+        self.check_table(n, dx + dth - 1)
+        nb = self.cfg.n_bars
+        theta = torch.empty((N, dth), dtype=torch.float32, device=self.device)
+        lp = torch.empty(N, dtype=torch.float32, device=self.device) if with_log_prob else None
+        probs = torch.empty((U, dth, nb), dtype=torch.float32, device=self.device)
+        borders = torch.empty((dth, nb + 1), dtype=torch.float32, device=self.device)
+        _check(self.lib, self.lib.npfn_ar_marginals(
+            self.h, _ptr(x_ctx), _ptr(theta_ctx), n, dx, dth, _ptr(x_unique), U, N, int(counter), int(row_base),
+            _ptr(theta), _ptr(lp), float(eps), _ptr(probs), _ptr(borders), self.stream), "npfn_ar_marginals")
+        self.n_features = dx + dth - 1
+        return theta, lp, probs, borders
 
     def ar_log_prob(self, x_ctx, theta_ctx, x_query, theta, eps: float = 1e-15,
                     x_unique: Optional[torch.Tensor] = None) -> torch.Tensor:

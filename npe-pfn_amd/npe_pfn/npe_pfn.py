@@ -31,6 +31,7 @@ from torch.distributions import Distribution
 from .accept_reject_sampler import accept_reject_sample
 from .diagnostics import bar_cdf
 from .kmeans import KMeansState
+from .marginals import PosteriorMarginals
 from .support_posterior import (get_filtering_method, latest_filtering, no_filtering,
                                 standardized_euclidean_filtering)
 from .tabpfn import TabPFNClassifier, TabPFNRegressor
@@ -323,6 +324,80 @@ class NPE_PFN_Core:
         dimension k exactly when conditional k is calibrated on the true pairs
         (:func:`npe_pfn.diagnostics.pit_ks_statistic`); needs no posterior samples."""
         return self._score_batched(theta, x, 1e-15, want_logp=False, want_cdf=True)[2]
+
+    def marginals(self, x: Tensor, num_draws: int = 10_000, max_sampling_batch_size: int = 10_000,
+                  return_samples: bool = False) -> PosteriorMarginals:
+        """Per-parameter posterior marginals q(theta_k | x) as bar distributions, averaged over the
+        conditionals of ``num_draws`` sampler draws per observation ("Rao-Blackwellised": the
+        mean over the draws of the full predictive distribution each theta_k was drawn from,
+        instead of a histogram of the draws; no extra forward pass).
+
+        ``x`` is [dx] or [1, dx] (one observation: the context is ``get_context(x)``, as in
+        :meth:`sample`) or [M, dx] (the context is the full table, as in :meth:`sample_batched`).
+        At most ``max_sampling_batch_size`` query rows go into one sampler call; the calls'
+        marginals are combined on the host in fp64, weighted by their draws.  Counters and Philox
+        rows advance as in :meth:`sample` / :meth:`sample_batched`.
+
+        The marginals are those of the estimator BEFORE truncation to the prior's support (the
+        rejection step of :meth:`sample` is not applied and nothing is reweighted);
+        ``support_fraction`` [M] reports the share of the draws inside the support, i.e. one
+        minus the estimator's leakage (NaN without a prior).  ``return_samples=True`` keeps the
+        draws as ``samples`` [M, num_draws, d_theta].  Results live on the sampler's device."""
+        x = self._validate_x(self._embed(x) if self.embedding_net else x)
+        num_draws, cap = int(num_draws), int(max_sampling_batch_size)
+        n_obs = x.shape[0]
+        if num_draws < 1 or cap < 1:
+            raise ValueError(f"marginals: num_draws ({num_draws}) and max_sampling_batch_size ({cap}) must be >= 1")
+        if n_obs == 1:
+            theta_ctx, x_ctx = self.get_context(x)
+        else:
+            theta_ctx, x_ctx = self._theta_train, self._x_train
+        per_call = max(1, cap // n_obs)
+        acc = borders = counts = None
+        draws = []
+        done = 0
+        with self._reuse_fits():
+            while done < num_draws:
+                d = min(per_call, num_draws - done)
+                # an observation shard of a larger batch draws at the unsharded batch's Philox rows
+                rb = self._obs_offset * d if n_obs > 1 else 0
+                if hasattr(self._model, "ar_marginals"):
+                    th, _, probs, bd = self._model.ar_marginals(x_ctx, theta_ctx, x, n_obs * d, row_base=rb)
+                else:
+                    th, probs, bd = self._marginals_generic(x_ctx, theta_ctx, x, d)
+                part = probs.to(torch.float64) * d
+                acc = part if acc is None else acc + part
+                borders = bd if borders is None else borders
+                if self.prior is not None:
+                    ok = self._within_support(th).reshape(n_obs, d).sum(1)
+                    counts = ok if counts is None else counts + ok.to(counts.device)
+                if return_samples:
+                    draws.append(th.reshape(n_obs, d, -1))
+                done += d
+        probs = (acc / num_draws).to(torch.float32)
+        frac = None if counts is None else counts.to(device=probs.device, dtype=torch.float64) / num_draws
+        return PosteriorMarginals(probs, borders, num_draws, frac,
+                                  engine=self._model.engine if self._fused() and probs.is_cuda else None,
+                                  samples=torch.cat(draws, 1) if return_samples else None)
+
+    def _marginals_generic(self, x_ctx: Tensor, theta_ctx: Tensor, x: Tensor, per: int):
+        """:meth:`_ar_generic` over ``x`` repeated obs-major ``per`` times, with every step's
+        predictive masses (softmax of the full logits, fp64) averaged over each observation's
+        rows: (theta [M * per, d_theta], probs [M, d_theta, n_bars] fp64, borders [d_theta, n_bars + 1])."""
+        joint = torch.cat([x_ctx, theta_ctx], dim=1)
+        dx = x_ctx.shape[1]
+        n_obs = x.shape[0]
+        feats = x.repeat_interleave(per, dim=0)
+        probs, borders = [], []
+        for k in range(theta_ctx.shape[1]):
+            self._model.fit(joint[:, : dx + k], joint[:, dx + k])
+            pred = self._model.predict(feats, output_type="full", quantiles=[])
+            draw = pred["criterion"].sample(pred["logits"])
+            p = torch.softmax(torch.as_tensor(pred["logits"]).to(torch.float64), dim=-1)
+            probs.append(p.reshape(n_obs, per, -1).mean(1))
+            borders.append(torch.as_tensor(pred["criterion"].borders).to(p.device))
+            feats = torch.cat([feats, draw[:, None].to(feats.device)], dim=1)
+        return feats[:, dx:], torch.stack(probs, 1), torch.stack(borders, 0)
 
     def _score_batched(self, theta: Tensor, x: Tensor, eps: float, want_logp: bool, want_cdf: bool):
         """(summed log density [...], per-step log densities [..., d_theta], PIT [..., d_theta]) of
@@ -654,6 +729,13 @@ class TabPFN_Based_Uncond_Estimator(NPE_PFN_Core):
         to score together; use :meth:`log_prob`."""
         raise NotImplementedError("TabPFN_Based_Uncond_Estimator has no observations to batch over (its x is a "
                                   "dummy column); use log_prob(theta)")
+
+    def marginals(self, x: Tensor = None, num_draws: int = 10_000, max_sampling_batch_size: int = 10_000,
+                  return_samples: bool = False):
+        """Not provided: every cluster is fitted on its own context and so has its own bar borders;
+        the mixture's marginal is not a column average on one grid."""
+        raise NotImplementedError("TabPFN_Based_Uncond_Estimator.marginals: the clusters' bar borders differ, so "
+                                  "their mixtures do not average on one grid")
 
     def pit_batched(self, theta: Tensor, x: Tensor = None) -> Tensor:
         """Not provided, for the reason given at :meth:`log_prob_batched`."""
