@@ -374,6 +374,35 @@ int npfn_restricted_box_round(npfn_engine* h, const float* low, const float* hig
                               int64_t n_rows, uint64_t seed, uint64_t counter, int64_t row_base, float* theta_out,
                               int64_t capacity, int64_t* counts, void* stream);
 
+/* Coverage ranks (NPE_PFN_Core.coverage_batched): folds one sampler round into per-observation
+ * integer counts, so that simulation-based-calibration, HPD and TARP ranks need no stored draws.
+ * theta [n_obs * per, dim] is obs-major (row i belongs to observation i / per: the layout of
+ * npfn_ar_sample_repeated's theta_out), logp [n_obs * per] the rows' log densities, take
+ * [n_obs * per] (may be NULL: every row) selects the rows that take part (take[i] != 0);
+ * theta_true [n_obs, dim], logp_true [n_obs], ref [n_obs, dim], inv_scale [dim].
+ * counts [n_obs, dim + 2, 2] int64 is ADDED to (the caller zeroes it before the first round);
+ * for observation m and each of its rows s that takes part, slot 0 counts "<" and slot 1 "==":
+ *  - column k < dim:  theta[s, k] < theta_true[m, k]   /  theta[s, k] == theta_true[m, k];
+ *  - column dim (HPD):  logp[s] > logp_true[m]          /  logp[s] == logp_true[m];
+ *  - column dim + 1 (TARP):  d2(theta[s]) < d2(theta_true[m])  /  ==, where
+ *    d2(a) = sum over k ascending of t_k * t_k, t_k = ((double)a_k - (double)ref[m, k]) *
+ *    (double)inv_scale[k], in fp64 with every multiply and add rounded on its own (no fused
+ *    multiply-add), so a host restatement gives the same bits
+ *    (npe_pfn.diagnostics.rank_accumulate_host).
+ * The comparisons are IEEE: a NaN on either side counts in neither slot.  logp / logp_true may
+ * both be NULL (the HPD column is left untouched), ref / inv_scale may both be NULL (the TARP
+ * column is left untouched).  Every observation is cut into strips of 256 rows, one workgroup
+ * each; a workgroup stages its rows through LDS (the table is read once, coalesced), counts per
+ * wave with a ballot, sums its waves in LDS and issues one 64-bit integer add per non-zero
+ * counter.  Integer sums do not depend on the order of arrival: the result is bitwise
+ * reproducible.  Any dim >= 1.  Asynchronous; n_obs * per == 0 launches nothing.
+ * Errors: NPFN_EINVAL (message starting "rank_accumulate") for n_obs < 0, per < 0, dim < 1, half
+ * of a nullable pair, or a missing theta / theta_true / counts -- all on the host before any
+ * launch. */
+int npfn_rank_accumulate(const float* theta, const float* logp, const uint8_t* take, int64_t n_obs, int64_t per,
+                         int32_t dim, const float* theta_true, const float* logp_true, const float* ref,
+                         const float* inv_scale, int64_t* counts, void* stream);
+
 /* K12 standardized-Euclidean context filter (support_posterior.py:357-369):
  * idx_out[0:k] = indices of the k rows of x [n_rows, dim] closest to obs in
  * z-scored Euclidean distance, ascending (ties by lower index). */

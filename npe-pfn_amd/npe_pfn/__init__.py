@@ -7,19 +7,24 @@ this directory (``npe-pfn_amd``) on ``sys.path``.  The TabPFN forward runs in
 the HIP engine ``npe_pfn/_lib/libnpfn.so`` (C-ABI: include/npfn.h).
 """
 
-from npe_pfn.diagnostics import bar_cdf, pit_ks_statistic
+from npe_pfn.diagnostics import (CoverageRanks, bar_cdf, expected_coverage, pit_ks_statistic, rank_accumulate_host,
+                                 rank_ks_statistic)
 from npe_pfn.marginals import PosteriorMarginals
 from npe_pfn.npe_pfn import NPE_PFN_Core, TabPFN_Based_NPE_PFN, TabPFN_Based_Uncond_Estimator
 from npe_pfn.restricted_prior import NPE_PFN_RestrictedPrior
 from npe_pfn.tsnpe_pfn import run_tsnpe_pfn
 
 __all__ = [
+    "CoverageRanks",
     "NPE_PFN_Core",
     "NPE_PFN_RestrictedPrior",
     "PosteriorMarginals",
     "TabPFN_Based_NPE_PFN",
     "TabPFN_Based_Uncond_Estimator",
     "bar_cdf",
+    "expected_coverage",
     "pit_ks_statistic",
+    "rank_accumulate_host",
+    "rank_ks_statistic",
     "run_tsnpe_pfn",
 ]

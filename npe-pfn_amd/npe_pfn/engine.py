@@ -103,6 +103,7 @@ SIGNATURES = {
     "npfn_predict_accept": (ctypes.c_int, [_vp, _vp, _i64, _i64, _f, _vp, _vp, _vp]),
     "npfn_restricted_box_round": (ctypes.c_int, [_vp, _vp, _vp, _i32, _f, _i64, _u64, _u64, _i64, _vp, _i64, _vp,
                                                  _vp]),
+    "npfn_rank_accumulate": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "npfn_filter_stdeuclid": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i64, _vp, _vp]),
     "npfn_sir_select": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _u64, _u64, _i64, _vp, _i32, _vp, _vp, _vp, _vp]),
     "npfn_kmeans_fit": (ctypes.c_int, [_vp, _i64, _i32, _i32, _u64, _i32, _f, _vp, _vp, _vp, _vp, _vp]),
@@ -637,6 +638,51 @@ class Engine:
             self.h, _ptr(low), _ptr(high), dim, float(threshold), int(n_rows), seed & 0xFFFFFFFFFFFFFFFF,
             int(counter) & 0xFFFFFFFFFFFFFFFF, int(row_base), _ptr(theta_out), capacity, _ptr(counts), self.stream),
             "npfn_restricted_box_round")
+
+    # ------------------------------------------------- coverage ranks (npfn_ranks.hip)
+    def rank_accumulate(self, theta, logp, take, n_obs: int, per: int, theta_true, logp_true, ref, inv_scale,
+                        counts: torch.Tensor) -> None:
+        """npfn_rank_accumulate: adds the counts of one sampler round to ``counts`` [n_obs, dim + 2,
+        2] (int64, on the engine's device, updated in place; zeroed by the caller before the first
+        round).  ``theta`` [n_obs * per, dim] obs-major, ``logp`` [n_obs * per], ``take`` [n_obs *
+        per] (bool / uint8, None = every row), ``theta_true`` [n_obs, dim], ``logp_true`` [n_obs],
+        ``ref`` [n_obs, dim], ``inv_scale`` [dim].  ``logp`` / ``logp_true`` may both be None (the
+        HPD column dim is left alone), ``ref`` / ``inv_scale`` too (the TARP column dim + 1).  The
+        definition of every count: :func:`npe_pfn.diagnostics.rank_accumulate_host`, which this
+        equals exactly.  ValueError for shapes that do not match, before the C call."""
+        n_obs, per = int(n_obs), int(per)
+        theta = _dev_f32(theta, self.device)
+        theta_true = _dev_f32(theta_true, self.device)
+        if n_obs < 0 or per < 0 or theta.ndim != 2 or theta.shape[1] < 1 or theta.shape[0] != n_obs * per:
+            raise ValueError(f"rank_accumulate: theta {tuple(theta.shape)} is not [{n_obs} * {per}, dim >= 1]")
+        dim = theta.shape[1]
+        if theta_true.shape != (n_obs, dim):
+            raise ValueError(f"rank_accumulate: theta_true {tuple(theta_true.shape)} is not [{n_obs}, {dim}]")
+        if (logp is None) != (logp_true is None) or (ref is None) != (inv_scale is None):
+            raise ValueError("rank_accumulate: logp / logp_true and ref / inv_scale are given in pairs")
+        if logp is not None:
+            logp = _dev_f32(logp, self.device).reshape(-1)
+            logp_true = _dev_f32(logp_true, self.device).reshape(-1)
+            if logp.shape[0] != n_obs * per or logp_true.shape[0] != n_obs:
+                raise ValueError(f"rank_accumulate: logp {tuple(logp.shape)} / logp_true {tuple(logp_true.shape)} "
+                                 f"do not match {n_obs} observations of {per} rows")
+        if ref is not None:
+            ref = _dev_f32(ref, self.device)
+            inv_scale = _dev_f32(inv_scale, self.device).reshape(-1)
+            if ref.shape != (n_obs, dim) or inv_scale.shape[0] != dim:
+                raise ValueError(f"rank_accumulate: ref {tuple(ref.shape)} / inv_scale {tuple(inv_scale.shape)} do "
+                                 f"not match [{n_obs}, {dim}] / [{dim}]")
+        if take is not None:
+            take = torch.as_tensor(take).to(device=self.device, dtype=torch.uint8).reshape(-1).contiguous()
+            if take.shape[0] != n_obs * per:
+                raise ValueError(f"rank_accumulate: take has {take.shape[0]} entries, theta {n_obs * per} rows")
+        if (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int64 or counts.device != self.device
+                or not counts.is_contiguous() or counts.shape != (n_obs, dim + 2, 2)):
+            raise ValueError(f"rank_accumulate: counts must be a contiguous int64 [{n_obs}, {dim + 2}, 2] tensor on "
+                             "the engine's device")
+        _check(self.lib, self.lib.npfn_rank_accumulate(_ptr(theta), _ptr(logp), _ptr(take), n_obs, per, dim,
+                                                       _ptr(theta_true), _ptr(logp_true), _ptr(ref), _ptr(inv_scale),
+                                                       _ptr(counts), self.stream), "npfn_rank_accumulate")
 
     def filter_stdeuclid(self, x: torch.Tensor, obs: torch.Tensor, k: int) -> torch.Tensor:
         x = _dev_f32(x, self.device)

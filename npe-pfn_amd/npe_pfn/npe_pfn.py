@@ -29,7 +29,7 @@ from torch import Tensor
 from torch.distributions import Distribution
 
 from .accept_reject_sampler import accept_reject_sample
-from .diagnostics import bar_cdf
+from .diagnostics import CoverageRanks, bar_cdf, rank_accumulate_host
 from .kmeans import KMeansState
 from .marginals import PosteriorMarginals
 from .support_posterior import (get_filtering_method, latest_filtering, no_filtering,
@@ -126,9 +126,20 @@ class NPE_PFN_Core:
         Only when the context is a deterministic function of x: a random filter draws a new
         subset per batch and the reference refits on each (npe_pfn.py:128, support_posterior.py:351)."""
         ctx = getattr(self._model, "reuse_fits", None)
-        if ctx is None or not self._context_is_deterministic():
+        if ctx is None or not self._context_is_deterministic() or getattr(self, "_fits_held", False):
+            # (inside a block that already holds a fit token -- coverage_batched scores and
+            # samples on one set of fits -- the inner call joins it)
             return contextlib.nullcontext()
-        return ctx()
+        return self._hold_fits(ctx)
+
+    @contextlib.contextmanager
+    def _hold_fits(self, ctx):
+        self._fits_held = True
+        try:
+            with ctx():
+                yield
+        finally:
+            self._fits_held = False
 
     # --------------------------------------------------- autoregressive core
     def _ar_generic(self, x_ctx: Tensor, theta_ctx: Tensor, x_query: Tensor, with_log_prob: bool,
@@ -287,14 +298,28 @@ class NPE_PFN_Core:
         return samples
 
     def log_prob(self, theta: Tensor, x: Tensor, max_sampling_batch_size: int = 10_000, mode: str = "autoregressive",
-                 eps: float = 1e-15, **ratio_kwargs) -> Tensor:
-        """log q(theta | x), in chunks of ``max_sampling_batch_size`` rows (reference :412-455)."""
+                 eps: float = 1e-15, *, leakage_correction: bool = False,
+                 support_fraction: Optional[Union[float, Tensor]] = None, num_rejection_samples: int = 10_000,
+                 **ratio_kwargs) -> Tensor:
+        """log q(theta | x), in chunks of ``max_sampling_batch_size`` rows (reference :412-455).
+
+        ``leakage_correction=True`` (autoregressive mode, needs a prior) returns the log density of
+        the posterior truncated to the prior's support, the distribution :meth:`sample` draws
+        from: ``log q - log(support_fraction)`` inside the support and ``-inf`` outside (the
+        correction the reference leaves as a TODO at ``_autoregressive_log_prob``).
+        ``support_fraction`` is taken as given, or estimated once per call by
+        :meth:`support_fraction` with ``num_rejection_samples`` draws (which advances the sample
+        counter).  The defaults change nothing."""
         if self.embedding_net:
             x = self._embed(x)
         theta = self._validate_theta(theta)
         x = self._validate_x(x)
         if mode not in ("autoregressive", "ratio_based"):
             raise ValueError(f"Invalid mode: {mode}")
+        if leakage_correction:
+            if mode != "autoregressive":
+                raise ValueError("log_prob: leakage_correction applies to mode='autoregressive' only")
+            log_frac = self._log_support_fraction(x, support_fraction, num_rejection_samples, 1)
         out = torch.zeros(theta.shape[0])
         with (self._reuse_fits() if mode == "autoregressive" else contextlib.nullcontext()):
             for i in range(0, theta.shape[0], max_sampling_batch_size):
@@ -304,9 +329,14 @@ class NPE_PFN_Core:
                 else:
                     out[i: i + max_sampling_batch_size] = self._ratio_based_log_prob(chunk, x, eps=eps,
                                                                                      **ratio_kwargs).cpu()
+        if leakage_correction:
+            out = out - log_frac.cpu().to(out.dtype)
+            out = torch.where(self._within_support(theta).cpu(), out, torch.full_like(out, float("-inf")))
         return out
 
-    def log_prob_batched(self, theta: Tensor, x: Tensor, eps: float = 1e-15, return_steps: bool = False):
+    def log_prob_batched(self, theta: Tensor, x: Tensor, eps: float = 1e-15, return_steps: bool = False, *,
+                         leakage_correction: bool = False, support_fraction: Optional[Tensor] = None,
+                         num_rejection_samples: int = 10_000):
         """Autoregressive log q(theta_m | x_m) of many (theta, x) pairs in one teacher-forced pass
         (the reference declares this method and leaves it unimplemented, :457-460).
 
@@ -314,9 +344,203 @@ class NPE_PFN_Core:
         observation) gives [M, K].  The context is the full table, as in ``sample_batched`` (no
         per-observation filter), so every autoregressive step is fitted once for all pairs.
         ``return_steps=True`` also returns the per-dimension log densities [..., d_theta], whose
-        sum over the last axis (in order) is the first result.  On the device of ``x``."""
+        sum over the last axis (in order) is the first result.  On the device of ``x``.
+
+        ``leakage_correction=True`` (needs a prior): the summed result becomes ``log q -
+        log(support_fraction)`` (the logarithm taken in fp64, rounded to the result's type) inside
+        the prior's support and ``-inf`` outside, as in :meth:`log_prob`; ``support_fraction`` [M]
+        is taken as given or estimated once per observation by :meth:`support_fraction` with
+        ``num_rejection_samples`` draws.  The per-step values are not corrected."""
+        if leakage_correction and self.prior is None:
+            raise ValueError("leakage_correction needs a prior: the correction is the prior support's share of q")
         lp, steps, _ = self._score_batched(theta, x, eps, want_logp=True, want_cdf=False)
+        if leakage_correction:
+            xv =self._validate_x(self._embed(x) if self.embedding_net else x)
+            log_frac = self._log_support_fraction(xv, support_fraction, num_rejection_samples, xv.shape[0])
+            log_frac = log_frac.to(device=lp.device, dtype=lp.dtype).reshape(-1, *([1] * (lp.ndim - 1)))
+            th = torch.as_tensor(theta)
+            inside = self._within_support(th.reshape(-1, th.shape[-1])).reshape(lp.shape).to(lp.device)
+            lp = torch.where(inside, lp - log_frac, torch.full_like(lp, float("-inf")))
         return (lp, steps) if return_steps else lp
+
+    def support_fraction(self, x: Tensor, num_draws: int = 10_000, max_sampling_batch_size: int = 10_000) -> Tensor:
+        """[M] float64: the share of ``num_draws`` unrejected sampler draws per observation that lie
+        inside the prior's support -- one minus the estimator's leakage, the normalising constant
+        of the truncated posterior that :meth:`sample` draws from.
+
+        ``x`` is [dx] or [1, dx] (the context is ``get_context(x)``, as in :meth:`sample`) or [M,
+        dx] (the full table, as in :meth:`sample_batched`); at most ``max_sampling_batch_size``
+        query rows go into one sampler call.  Plain sampler calls: the sample counter advances as
+        in :meth:`sample`.  On the device of ``x``.  ValueError without a prior."""
+        if self.prior is None:
+            raise ValueError("support_fraction: the estimator has no prior, so there is no support to leak from")
+        x = self._validate_x(self._embed(x) if self.embedding_net else x)
+        return self._support_fraction(x, int(num_draws), int(max_sampling_batch_size))
+
+    def _support_fraction(self, x: Tensor, num_draws: int, cap: int) -> Tensor:
+        """:meth:`support_fraction` of an ``x`` that is already embedded and validated."""
+        n_obs = x.shape[0]
+        if num_draws < 1 or cap < 1:
+            raise ValueError(f"support_fraction: num_draws ({num_draws}) and max_sampling_batch_size ({cap}) must "
+                             "be >= 1")
+        if n_obs == 1:
+            theta_ctx, x_ctx = self.get_context(x)
+        else:
+            theta_ctx, x_ctx = self._theta_train, self._x_train
+        per_call = max(1, cap // n_obs)
+        counts = None
+        done = 0
+        with self._reuse_fits():
+            while done < num_draws:
+                d = min(per_call, num_draws - done)
+                rb = self._obs_offset * d if n_obs > 1 else 0
+                th, _ = self._ar(x_ctx, theta_ctx, x.repeat_interleave(d, dim=0), False, 1e-15, row_base=rb,
+                                 x_unique=x)
+                ok = self._within_support(th).reshape(n_obs, d).sum(1)
+                counts = ok if counts is None else counts + ok.to(counts.device)
+                done += d
+        return counts.to(device=x.device, dtype=torch.float64) / num_draws
+
+    def _log_support_fraction(self, x: Tensor, given, num_draws: int, n_obs: int) -> Tensor:
+        """log of the support fraction of each of ``n_obs`` observations (float64 [n_obs]): ``given``
+        if passed, else :meth:`support_fraction` of ``x``.  ValueError without a prior, for a wrong
+        number of fractions, or for a fraction of 0 (nothing to normalise by)."""
+        if self.prior is None:
+            raise ValueError("leakage_correction needs a prior: the correction is the prior support's share of q")
+        if given is None:
+            frac = self._support_fraction(x, int(num_draws), 10_000)
+        else:
+            frac = torch.as_tensor(given, dtype=torch.float64).reshape(-1)
+            if frac.numel() == 1 and n_obs > 1:
+                frac = frac.expand(n_obs)
+        if frac.numel() != n_obs:
+            raise ValueError(f"support_fraction has {frac.numel()} entries for {n_obs} observation(s)")
+        if not bool((frac > 0).all()):
+            raise ValueError("leakage_correction: a support fraction of 0 (no draw inside the prior's support) "
+                             "cannot normalise the density")
+        return torch.log(frac)
+
+    def coverage_batched(self, theta_true: Tensor, x: Tensor, num_posterior_samples: int = 1000,
+                         references: Optional[Tensor] = None, max_sampling_batch_size: int = 10_000,
+                         oversample_factor: float = 1.5, eps: float = 1e-15,
+                         return_samples: bool = False) -> CoverageRanks:
+        """Coverage ranks of M true parameters among ``num_posterior_samples`` posterior draws each:
+        simulation-based-calibration ranks per parameter, the HPD rank (draws denser than the
+        truth) and the TARP rank (draws closer to a reference point than the truth), as a
+        :class:`npe_pfn.diagnostics.CoverageRanks` (:func:`~npe_pfn.diagnostics.rank_ks_statistic`
+        and :func:`~npe_pfn.diagnostics.expected_coverage` read it).
+
+        ``theta_true`` [M, d_theta] (finite), ``x`` [M, dx]; the context is the full table, as in
+        :meth:`sample_batched` / :meth:`log_prob_batched`.  Observations go in blocks of ``max(1,
+        max_sampling_batch_size // int(S * oversample_factor))``; a block scores its truths and
+        draws on one set of fits, with :meth:`sample_batched`'s rounds and selection rule (an
+        observation keeps its first S accepted draws in order), and every round is folded into
+        integer counts as it is produced (``npfn_rank_accumulate`` on the engine,
+        :func:`~npe_pfn.diagnostics.rank_accumulate_host` otherwise): without
+        ``return_samples=True`` no [M, S, ...] buffer exists.  The sample counter advances as
+        ``sample_batched`` on each block in turn would advance it, and the draws are those calls'.
+
+        With a prior, all ranks refer to the posterior truncated to the prior's support, the
+        draws ``sample_batched`` returns.  The truncation divides the density of the truth and of
+        every draw of one observation by the same support fraction, so the constant cancels in
+        the HPD comparison and the uncorrected log densities are compared (``log_prob_true`` is
+        :meth:`log_prob_batched`'s, uncorrected).
+
+        TARP ``references`` [M, d_theta]: as given; by default ``prior.sample((M,))``, without a
+        prior uniform between the per-dimension minimum and maximum of the context thetas (CPU
+        torch generator).  Distances are scaled per dimension by ``inv_scale`` = 1 / (max - min)
+        of the context thetas (1 where they coincide).  RuntimeError when an observation is still
+        short after 10 rounds, like ``sample_batched``.  Results on the device of ``x``."""
+        x = self._validate_x(self._embed(x) if self.embedding_net else x)
+        theta_true = torch.as_tensor(theta_true)
+        n_obs, dth = x.shape[0], self._theta_train.shape[1]
+        if theta_true.ndim != 2 or theta_true.shape != (n_obs, dth):
+            raise ValueError(f"coverage_batched: theta_true {tuple(theta_true.shape)} is not [{n_obs}, {dth}] (one "
+                             "true parameter per row of x)")
+        if not bool(torch.isfinite(theta_true).all()):
+            raise ValueError("coverage_batched: theta_true has non-finite entries")
+        n, cap = int(num_posterior_samples), int(max_sampling_batch_size)
+        if n < 1 or cap < 1:
+            raise ValueError(f"coverage_batched: num_posterior_samples ({n}) and max_sampling_batch_size ({cap}) "
+                             "must be >= 1")
+        ctx_lo = self._theta_train.min(dim=0).values.to(torch.float32)
+        ctx_hi = self._theta_train.max(dim=0).values.to(torch.float32)
+        span = ctx_hi - ctx_lo
+        inv_scale = torch.where(span > 0, 1.0 / torch.where(span > 0, span, torch.ones_like(span)),
+                                torch.ones_like(span))
+        if references is not None:
+            references = torch.as_tensor(references)
+            if references.shape != (n_obs, dth):
+                raise ValueError(f"coverage_batched: references {tuple(references.shape)} is not [{n_obs}, {dth}]")
+        elif self.prior is not None:
+            references = self.prior.sample((n_obs,)).reshape(n_obs, dth)
+        else:
+            references = ctx_lo.cpu() + torch.rand(n_obs, dth) * span.cpu()
+        references = references.to(torch.float32)
+        per_round = int(n * oversample_factor) if self.prior is not None else n
+        block = max(1, cap // max(1, int(n * oversample_factor)))
+        parts = []
+        for a in range(0, n_obs, block):
+            b = min(n_obs, a + block)
+            with self._reuse_fits():
+                parts.append(self._coverage_block(theta_true[a:b], x[a:b], references[a:b], inv_scale, n, per_round,
+                                                  eps, return_samples))
+        dev = x.device
+        cat = [None if p[0] is None else torch.cat(p, 0).to(dev) for p in zip(*parts)]
+        counts, lp_true, samples, sample_lp = cat
+        return CoverageRanks(counts[:, :, 0].contiguous(), counts[:, :, 1].contiguous(), n, lp_true,
+                             references.to(dev), inv_scale.to(dev), samples, sample_lp)
+
+    def _coverage_block(self, theta_true, x, references, inv_scale, n, per_round, eps, return_samples):
+        """One block of :meth:`coverage_batched` under one fit token: (counts [B, d_theta + 2, 2],
+        log_prob_true [B], samples or None, sample_log_probs or None), on the sampler's device
+        except ``log_prob_true`` (the device of ``x``)."""
+        n_obs, dth = theta_true.shape
+        lp_true, _, _ = self._score_batched(theta_true, x, eps, want_logp=True, want_cdf=False)
+        counts = need = filled = out_th = out_lp = None
+        for _ in range(10):
+            if need is not None and int(need.sum()) == 0:
+                break
+            th, lp = self._sample_batched(x, per_round, with_log_prob=True, eps=eps)
+            dev = th.device
+            lp = lp.to(dev)
+            if counts is None:
+                counts = torch.zeros((n_obs, dth + 2, 2), dtype=torch.int64, device=dev)
+                need = torch.full((n_obs,), n, dtype=torch.int64, device=dev)
+                filled = torch.zeros(n_obs, dtype=torch.int64, device=dev)
+                truth = [t.to(dev).contiguous() for t in (theta_true, lp_true, references, inv_scale)]
+                if return_samples:
+                    out_th = torch.empty(n_obs, n, dth, dtype=th.dtype, device=dev)
+                    out_lp = torch.empty(n_obs, n, dtype=lp.dtype, device=dev)
+            if self.prior is None:
+                sel, taken = None, torch.full_like(need, per_round)
+            else:
+                # sample_batched's selection: an observation keeps its first accepted draws in order
+                ok = self._within_support(th.reshape(n_obs * per_round, -1)).reshape(n_obs, per_round).to(dev)
+                rank = torch.cumsum(ok.to(torch.int64), 1) - 1
+                sel = ok & (rank < need[:, None])
+                taken = sel.sum(1)
+            if self._fused() and dev.type == "cuda":
+                fold = self._model.engine.rank_accumulate
+            else:
+                fold = rank_accumulate_host
+            fold(th.reshape(n_obs * per_round, dth), lp.reshape(-1), None if sel is None else sel.reshape(-1), n_obs,
+                 per_round, truth[0], truth[1], truth[2], truth[3], counts)
+            if return_samples:
+                if sel is None:
+                    out_th.copy_(th)
+                    out_lp.copy_(lp)
+                else:
+                    oi, ri = sel.nonzero(as_tuple=True)
+                    dest = filled[oi] + rank[oi, ri]
+                    out_th[oi, dest] = th[oi, ri]
+                    out_lp[oi, dest] = lp[oi, ri]
+            filled += taken
+            need -= taken
+        if int(need.sum()) != 0:
+            raise RuntimeError(f"coverage_batched: {int((need > 0).sum())} observation(s) got fewer than {n} samples "
+                               "inside the prior support after 10 rounds")
+        return counts, lp_true, out_th, out_lp
 
     def pit_batched(self, theta: Tensor, x: Tensor) -> Tensor:
         """Per-dimension probability integral transform u_k = F_k(theta_k | x, theta_<k) of the
@@ -741,6 +965,11 @@ class TabPFN_Based_Uncond_Estimator(NPE_PFN_Core):
         """Not provided, for the reason given at :meth:`log_prob_batched`."""
         raise NotImplementedError("TabPFN_Based_Uncond_Estimator has no observations to batch over (its x is a "
                                   "dummy column)")
+
+    def coverage_batched(self, theta_true: Tensor, x: Tensor = None, *args, **kwargs):
+        """Not provided, for the reason given at :meth:`log_prob_batched`."""
+        raise NotImplementedError("TabPFN_Based_Uncond_Estimator has no observations to batch over (its x is a "
+                                  "dummy column); use log_prob(theta)")
 
     def log_prob(self, theta: Tensor, x: Tensor = None, max_sampling_batch_size: int = 10_000,
                  mode: str = "autoregressive", eps: float = 1e-15, **ratio_kwargs) -> Tensor:
