@@ -277,6 +277,42 @@ int npfn_ar_marginals(npfn_engine* h, const float* x_ctx, const float* theta_ctx
                       int64_t n_rows, uint64_t counter, int64_t row_base, float* theta_out,
                       float* log_prob_out, float eps, float* marg_out, float* borders_out, void* stream);
 
+/* npfn_ar_sample_repeated that also returns the 2-D posterior marginals of every pair of
+ * parameters on a grid of n_cells x n_cells cells ("half Rao-Blackwellised": the earlier
+ * coordinate of a pair is the draw's cell, the later one is integrated out of the row's
+ * conditional instead of being sampled).  Arguments, fits, fit reuse, side-stream prefit, chunking
+ * and step 0 once per distinct row as npfn_ar_marginals up to eps; theta_out / log_prob_out (either
+ * may be NULL) are bit for bit those of npfn_ar_sample_repeated.  With G = n_cells, per = n_rows /
+ * n_unique, edges [dim_theta, G + 1] (DEVICE, row k strictly increasing: the cell borders of
+ * parameter k; not checked here) and w_i[k][c] = npfn_bar_cell_mass of the mixture row i draws
+ * theta_k from, on step k's borders and edges[k]:
+ *  - cell_out [n_unique, dim_theta, G]: [u, k, c] = (1 / per) * sum over the rows i of
+ *    observation u of w_i[k][c] -- the 1-D marginal's cell masses (at step 0 the distinct row's
+ *    own cell masses);
+ *  - pair_out [n_unique, n_pairs, G, G], n_pairs = dim_theta (dim_theta - 1) / 2, pair (j, k),
+ *    j < k, at index k (k - 1) / 2 + j: [u, (j, k), a, c] = (1 / per) * sum over the rows i of
+ *    observation u whose draw theta_j lies in cell a of edges[j] (edges[j][a] <= theta_j <
+ *    edges[j][a + 1]) of w_i[k][c].  Mass outside the limits of either parameter is left out, so
+ *    a table sums to the share of the joint inside its limits.  May be NULL when dim_theta == 1.
+ * Route: every window of rows goes k_mix_prob -> window -> k_group_sample(per = 1) as in
+ * npfn_ar_marginals, then npfn_bar_cell_mass and npfn_pair_accumulate on the window; each step's
+ * sums are divided by 2^40 per and rounded to fp32 once.  The sums are integers, so the result
+ * is bitwise reproducible and independent of npfn_set_chunk_rows, and an observation's tables do
+ * not depend on which other observations share the call (given the same row_base for its rows).
+ * An observation with a row whose mixture has no mass gets NaN tables for that step.
+ * Device memory owned by the engine: npfn_ar_marginals' fp32 window, a [max(chunk rows,
+ * n_unique), G] fp64 window of cell masses and [n_unique, (dim_theta - 1) G G + G] int64 sums,
+ * zeroed by every call.  Asynchronous.
+ * Errors, on the host before the engine is touched: NPFN_EINVAL for n_unique < 1, n_rows <
+ * n_unique, n_unique not dividing n_rows, n_cells outside 2..128, per > 2^22 (the int64 headroom
+ * of the 2^40-scaled sums), NULL edges or cell_out, NULL pair_out with dim_theta > 1; then
+ * whatever npfn_ar_sample_repeated rejects; NPFN_ESTATE on a partial estimator range. */
+int npfn_ar_pair_marginals(npfn_engine* h, const float* x_ctx, const float* theta_ctx, int64_t n_ctx,
+                           int32_t dim_x, int32_t dim_theta, const float* x_unique, int64_t n_unique,
+                           int64_t n_rows, uint64_t counter, int64_t row_base, float* theta_out,
+                           float* log_prob_out, float eps, const float* edges, int32_t n_cells,
+                           float* pair_out, float* cell_out, void* stream);
+
 /* Teacher-forced autoregressive log density (npe_pfn.py:462-524):
  * log_prob_out [n_rows] = sum_k -NLL_k(theta[:, k] | x, theta[:, :k]). */
 int npfn_ar_log_prob(npfn_engine* h, const float* x_ctx, const float* theta_ctx, int64_t n_ctx,
@@ -402,6 +438,48 @@ int npfn_restricted_box_round(npfn_engine* h, const float* low, const float* hig
 int npfn_rank_accumulate(const float* theta, const float* logp, const uint8_t* take, int64_t n_obs, int64_t per,
                          int32_t dim, const float* theta_true, const float* logp_true, const float* ref,
                          const float* inv_scale, int64_t* counts, void* stream);
+
+/* Cell masses of bar distributions on a coarse grid (the row kernel of npfn_ar_pair_marginals;
+ * needs no engine).  probs [n_rows, n_bars]: UNNORMALISED fp32 bar masses (a k_mix_prob row, or
+ * exp of logits); borders [n_bars + 1], shared by all rows; edges [n_cells + 1] fp32, strictly
+ * increasing (not checked).  w_out [n_rows, n_cells] in FP64: with tot = sum_b p[b] and L(j) =
+ * sum_{b<j} p[b] (both fp64; per thread in bar order, then an LDS block scan in a fixed order),
+ *   F(e) = (L(j) + p[j] * frac) / tot,   w[c] = max(F(edges[c + 1]) - F(edges[c]), 0),
+ * j = the bucket of e by npfn_bar_nll's rule and frac the share of bar j left of e by
+ * npfn_bar_cdf's rules: linear in an inner bar, erfc / erf of the half-normal tails in the two
+ * end bars, 1 in a bar of width 0.  F is always formed from the left (the sums are fp64).  A
+ * row whose tot is not a positive finite number gets NaN in its whole w row.  One 256-thread
+ * workgroup per row.  Asynchronous.
+ * Errors (host, before any launch): NPFN_EINVAL (message starting "bar_cell_mass") for n_rows <
+ * 0 or >= 2^31, n_bars < 2 or beyond what a workgroup's LDS holds (15 000), n_cells outside
+ * 2..128, or a NULL pointer. */
+int npfn_bar_cell_mass(const float* probs, const float* borders, int64_t n_rows, int32_t n_bars,
+                       const float* edges, int32_t n_cells, double* w_out, void* stream);
+
+/* Folds one window of cell masses into the integer sums behind npfn_ar_pair_marginals (needs no
+ * engine).  With G = n_cells: w [n_rows, G] fp64 (npfn_bar_cell_mass), theta [n_rows, ldt] whose
+ * first n_prev columns are the rows' earlier draws, edges [n_prev, G + 1] (row j strictly
+ * increasing); window row r is row r0 + r of the call and belongs to observation u = (r0 + r) /
+ * per.  Every w is quantised once, q = llrint(w * 2^40) (round half to even), and for row r:
+ *  - cellQ [U, G]: cellQ[u][c] += q[c] for every c;
+ *  - pairQ [U, n_prev, G, G]: for every j < n_prev whose draw has a cell a (edges[j][a] <=
+ *    theta[r][j] < edges[j][a + 1]): pairQ[u][j][a][c] += q[c] for every c.  A draw below
+ *    edges[j][0], at or above edges[j][G], or NaN has no cell;
+ *  - a row with a NaN in w sets bad[u] = 1 (bad [U] int32) and adds nothing.
+ * Both tables are ADDED to (int64; the caller zeroes them and bad before the first window).
+ * npe_pfn.pair_marginals.pair_accumulate_host is the same statement in torch; the two are equal
+ * exactly.  Kernel: one workgroup per (strip of 256 consecutive rows of an observation, j, slab
+ * of at most 4096 / G values of a); it finds the rows' cells by binary search, adds into an
+ * int64 LDS table with 64-bit LDS integer adds and issues one 64-bit global integer add per
+ * non-zero cell.  Integer sums do not depend on the order of arrival: the result is bitwise
+ * reproducible whatever the windows, the launch geometry or the other observations of the call.
+ * n_prev = 0 (theta, edges and pairQ may be NULL) adds to cellQ only.  Asynchronous.
+ * Errors (host, before any launch): NPFN_EINVAL (message starting "pair_accumulate") for r0 < 0,
+ * n_rows < 0, per < 1, per > 2^22 (the int64 headroom: 2^22 rows x 2^40 < 2^63), n_prev < 0 or
+ * > ldt, n_cells outside 2..128, or a missing pointer. */
+int npfn_pair_accumulate(const double* w, const float* theta, int64_t ldt, int32_t n_prev, const float* edges,
+                         int32_t n_cells, int64_t r0, int64_t n_rows, int64_t per, int64_t* pairQ,
+                         int64_t* cellQ, int32_t* bad, void* stream);
 
 /* K12 standardized-Euclidean context filter (support_posterior.py:357-369):
  * idx_out[0:k] = indices of the k rows of x [n_rows, dim] closest to obs in

@@ -184,6 +184,10 @@ struct npfn_engine {
   // npfn_ar_marginals: [chunk rows][nb] row mixtures of a chunk, [rows] fp64 1 / row sums,
   // [n_unique * strips][nb] fp64 strip partials of the step in flight
   DevBuf margwin, marginv, margpart;
+  // npfn_ar_pair_marginals: [max(chunk rows, n_unique)][G] fp64 cell masses of a window; the
+  // step's int64 tables pairQ [n_unique][dim_theta - 1][G][G] and cellQ [n_unique][G] followed by
+  // the int32 flags bad [n_unique]; [nb + 1] borders of the step in flight
+  DevBuf pairw, pairtab, pairbd;
   DevBuf mixlog, borders;  // npfn_predict_stats: [kStatsRows][nb] mixture logits of a row window, [nb + 1] borders
   // npfn_predict_accept / npfn_restricted_box_round: [chunk rows][n_classes] probabilities of a
   // chunk; [n_rows][dim] proposals and [n_rows] accept flags of a round
@@ -1264,11 +1268,21 @@ int ar_step_fit(npfn_engine* h, const float* joint, int Ft, int64_t n, int dx, i
 // pass through the window margwin -- k_mix_prob writes a chunk's masses, k_group_sample with
 // per = 1 draws from them (k_mix_sample's draw, bit for bit) and launch_marg_accum adds them to
 // the observations' sums; step 0's marginal is the distinct row's own mixture.
+// npfn_ar_pair_marginals (po set, n_unique >= 1) takes the same window route: every window's
+// mixtures are re-binned onto the step's G cells (launch_bar_cell_mass) and folded, keyed by the
+// cells of the rows' earlier draws, into the step's integer tables (launch_pair_accumulate),
+// which launch_pair_final turns into pair (j, k), j < k, and the cell masses of dimension k.
+struct PairOut {
+  const float* edges;  // [dim_theta][G + 1]
+  int G;
+  float* pair_out;     // [n_unique][dim_theta (dim_theta - 1) / 2][G][G]
+  float* cell_out;     // [n_unique][dim_theta][G]
+};
 int ar_sample_impl(npfn_engine* h, const float* x_ctx, const float* theta_ctx, int64_t n_ctx, int dim_x,
                    int dim_theta, const float* x_query, int64_t n_unique, int64_t n_rows, uint64_t counter,
                    int64_t row_base, float* theta_out, float* log_prob_out, float eps, hipStream_t s,
-                   float* marg_out = nullptr, float* borders_out = nullptr) {
-  if (!theta_out && !marg_out) return fail(NPFN_EINVAL, "ar_sample: null theta_out");
+                   float* marg_out = nullptr, float* borders_out = nullptr, const PairOut* po = nullptr) {
+  if (!theta_out && !marg_out && !po) return fail(NPFN_EINVAL, "ar_sample: null theta_out");
   if (row_base < 0) return fail(NPFN_EINVAL, "ar_sample: negative row_base");
   RCHK(need_full_range(h, "ar_sample"));
   RCHK(ensure_pipelines(h, false));
@@ -1287,6 +1301,21 @@ int ar_sample_impl(npfn_engine* h, const float* x_ctx, const float* theta_ctx, i
     RCHK(ensure(h->marginv, (size_t)std::max(win_rows, n_unique) * sizeof(double), s));
     RCHK(ensure(h->margpart, (size_t)n_unique * marg_strips(per) * nb * sizeof(double), s));
   }
+  const int G = po ? po->G : 0;
+  const int64_t GG = (int64_t)G * G, n_pairs = (int64_t)dim_theta * (dim_theta - 1) / 2;
+  const size_t pair_q = (size_t)n_unique * ((size_t)std::max(dim_theta - 1, 0) * GG + G);  // int64 sums per step
+  int64_t *pairQ = nullptr, *cellQ = nullptr;
+  int32_t* pbad = nullptr;
+  if (po) {
+    if (nb > cell_mass_max_bars()) return fail(NPFN_EINVAL, "ar_pair_marginals: too many bars for the re-binning");
+    RCHK(ensure(h->margwin, (size_t)win_rows * nb * sizeof(float), s));
+    RCHK(ensure(h->pairw, (size_t)std::max(win_rows, n_unique) * G * sizeof(double), s));
+    RCHK(ensure(h->pairtab, pair_q * sizeof(int64_t) + (size_t)n_unique * sizeof(int32_t), s));
+    RCHK(ensure(h->pairbd, (size_t)(nb + 1) * sizeof(float), s));
+    pairQ = (int64_t*)h->pairtab.p;
+    cellQ = pairQ + (size_t)n_unique * std::max(dim_theta - 1, 0) * GG;
+    pbad = (int32_t*)(pairQ + pair_q);
+  }
   begin_ar_fits(h, n_ctx, dim_x, dim_theta, reuse);
   if (!reuse) RCHK(ar_prefit(h, joint, Ft, n_ctx, dim_x, dim_theta, s, piped));
   for (int k = 0; k < dim_theta; ++k) {
@@ -1294,6 +1323,10 @@ int ar_sample_impl(npfn_engine* h, const float* x_ctx, const float* theta_ctx, i
     h->f = step_fit(h, k);
     if (!reuse) RCHK(ar_step_fit(h, joint, Ft, n_ctx, dim_x, dim_theta, k, piped, s));
     if (marg_out) launch_borders(h->bz, (const float*)h->f->ystats.p, nb, borders_out + (int64_t)k * (nb + 1), s);
+    if (po && n_rows > 0) {  // this step's borders and zeroed tables
+      launch_borders(h->bz, (const float*)h->f->ystats.p, nb, (float*)h->pairbd.p, s);
+      HIPCHK(hipMemsetAsync(h->pairtab.p, 0, pair_q * sizeof(int64_t) + (size_t)n_unique * sizeof(int32_t), s));
+    }
     if (k == 0 && n_unique > 0 && n_rows > 0) {
       RCHK(ensure(h->pu, (size_t)n_unique * nb * sizeof(float), s));
       float* pu = (float*)h->pu.p;
@@ -1308,6 +1341,13 @@ int ar_sample_impl(npfn_engine* h, const float* x_ctx, const float* theta_ctx, i
         launch_marg_accum(pu, 0, n_unique, 1, nb, (double*)h->marginv.p, (double*)h->margpart.p, s);
         launch_marg_final((const double*)h->margpart.p, n_unique, 1, nb, marg_out, (int64_t)dim_theta * nb, s);
       }
+      if (po) {  // no pairs at step 0: the distinct row's own cell masses
+        ProfGuard g(h, P_OTHER, 0.0, (double)n_unique * (nb * 4 + G * 24), s);
+        launch_bar_cell_mass(pu, (const float*)h->pairbd.p, n_unique, nb, po->edges, G, (double*)h->pairw.p, s);
+        launch_pair_accumulate((const double*)h->pairw.p, nullptr, 0, 0, nullptr, G, 0, n_unique, 1, pairQ, cellQ,
+                               pbad, s);
+        launch_pair_final(cellQ, pbad, n_unique, G, 1, po->cell_out, (int64_t)dim_theta * G, s);
+      }
       ProfGuard g(h, P_MIX_SAMPLE, 0.0, (double)n_rows * nb * 4, s);
       launch_group_sample(pu, per, n_rows, nb, h->bz, (const float*)h->f->ystats.p, h->cfg.random_state,
                           counter + (uint64_t)k, 0, (uint64_t)row_base, feat, Ft, F, logp, log_eps, s);
@@ -1316,7 +1356,7 @@ int ar_sample_impl(npfn_engine* h, const float* x_ctx, const float* theta_ctx, i
     for (int64_t r0 = 0; r0 < n_rows; r0 += h->chunk_rows) {
       const int64_t rows = std::min(h->chunk_rows, n_rows - r0);
       RCHK(predict_logits_chunk(h, feat + r0 * Ft, Ft, rows, s));
-      if (marg_out) {
+      if (marg_out || po) {
         float* win = (float*)h->margwin.p;
         {
           ProfGuard g(h, P_MIX_SAMPLE, 0.0, (double)E * rows * nb * sizeof(logit_t) + (double)rows * nb * 8, s);
@@ -1328,7 +1368,13 @@ int ar_sample_impl(npfn_engine* h, const float* x_ctx, const float* theta_ctx, i
                               counter + (uint64_t)k, r0, (uint64_t)row_base, feat, Ft, F, logp, log_eps, s);
         }
         ProfGuard g(h, P_OTHER, 0.0, (double)rows * nb * 8, s);
-        launch_marg_accum(win, r0, rows, per, nb, (double*)h->marginv.p, (double*)h->margpart.p, s);
+        if (marg_out) launch_marg_accum(win, r0, rows, per, nb, (double*)h->marginv.p, (double*)h->margpart.p, s);
+        if (po) {  // the draws of this window are in feat by now (stream order)
+          launch_bar_cell_mass(win, (const float*)h->pairbd.p, rows, nb, po->edges + (int64_t)k * (G + 1), G,
+                               (double*)h->pairw.p, s);
+          launch_pair_accumulate((const double*)h->pairw.p, feat + r0 * Ft + dim_x, Ft, k, po->edges, G, r0, rows, per,
+                                 pairQ, cellQ, pbad, s);
+        }
         continue;
       }
       ProfGuard g(h, P_MIX_SAMPLE, 0.0, (double)E * rows * nb * sizeof(logit_t), s);
@@ -1340,6 +1386,11 @@ int ar_sample_impl(npfn_engine* h, const float* x_ctx, const float* theta_ctx, i
       ProfGuard g(h, P_OTHER, 0.0, (double)n_unique * marg_strips(per) * nb * 8, s);
       launch_marg_final((const double*)h->margpart.p, n_unique, per, nb, marg_out + (int64_t)k * nb,
                         (int64_t)dim_theta * nb, s);
+    }
+    if (po) {
+      ProfGuard g(h, P_OTHER, 0.0, (double)n_unique * (k * GG + G) * 12, s);
+      launch_pair_final(pairQ, pbad, n_unique, k * GG, per, po->pair_out + (int64_t)k * (k - 1) / 2 * GG, n_pairs * GG, s);
+      launch_pair_final(cellQ, pbad, n_unique, G, per, po->cell_out + (int64_t)k * G, (int64_t)dim_theta * G, s);
     }
   }
   end_ar_fits(h, n_ctx, dim_x, dim_theta);
@@ -1573,7 +1624,7 @@ int npfn_engine_destroy(npfn_engine* h) {
   h->wmain.release();
   h->wside.release();
   DevBuf* bufs[] = {&h->dh,      &h->logits, &h->tgt,
-                    &h->joint, &h->feat,     &h->logp, &h->pu, &h->margwin, &h->marginv, &h->margpart, &h->mixlog, &h->borders, &h->rp_probs, &h->rp_theta, &h->rp_mask, &h->views, &h->ftype, &h->ett,     &h->fp_salt};
+                    &h->joint, &h->feat,     &h->logp, &h->pu, &h->margwin, &h->marginv, &h->margpart, &h->pairw, &h->pairtab, &h->pairbd, &h->mixlog, &h->borders, &h->rp_probs, &h->rp_theta, &h->rp_mask, &h->views, &h->ftype, &h->ett,     &h->fp_salt};
   for (DevBuf* b : bufs) free_buf(*b);
   delete h;
   return NPFN_OK;
@@ -1832,6 +1883,22 @@ int npfn_ar_marginals(npfn_engine* h, const float* x_ctx, const float* theta_ctx
   RCHK(check_engine(h));
   return ar_sample_impl(h, x_ctx, theta_ctx, n_ctx, dim_x, dim_theta, x_unique, n_unique, n_rows, counter, row_base,
                         theta_out, log_prob_out, eps, (hipStream_t)stream, marg_out, borders_out);
+}
+
+int npfn_ar_pair_marginals(npfn_engine* h, const float* x_ctx, const float* theta_ctx, int64_t n_ctx, int32_t dim_x,
+                           int32_t dim_theta, const float* x_unique, int64_t n_unique, int64_t n_rows,
+                           uint64_t counter, int64_t row_base, float* theta_out, float* log_prob_out, float eps,
+                           const float* edges, int32_t n_cells, float* pair_out, float* cell_out, void* stream) {
+  // host checks first: they answer without an engine or a device
+  if (n_unique < 1 || n_rows < n_unique || n_rows % n_unique != 0)
+    return fail(NPFN_EINVAL, "ar_pair_marginals: need n_unique >= 1 dividing n_rows >= n_unique");
+  RCHK(pair_check_cells(n_cells, n_rows / n_unique, "ar_pair_marginals"));
+  if (!edges || !cell_out || (!pair_out && dim_theta > 1))
+    return fail(NPFN_EINVAL, "ar_pair_marginals: null edges, pair_out or cell_out");
+  RCHK(check_engine(h));
+  const PairOut po{edges, n_cells, pair_out, cell_out};
+  return ar_sample_impl(h, x_ctx, theta_ctx, n_ctx, dim_x, dim_theta, x_unique, n_unique, n_rows, counter, row_base,
+                        theta_out, log_prob_out, eps, (hipStream_t)stream, nullptr, nullptr, &po);
 }
 
 int npfn_ar_log_prob(npfn_engine* h, const float* x_ctx, const float* theta_ctx, int64_t n_ctx, int32_t dim_x,

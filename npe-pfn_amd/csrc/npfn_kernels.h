@@ -322,6 +322,26 @@ void launch_marg_accum(const float* win, int64_t r0, int64_t rows, int64_t per, 
                        hipStream_t s);
 void launch_marg_final(const double* part, int64_t n_unique, int64_t per, int nb, float* out, int64_t ldo,
                        hipStream_t s);
+// npfn_pairs.hip (npfn_ar_pair_marginals): 2-D marginals on a grid of G cells per dimension.
+// launch_bar_cell_mass: w[r][c] (fp64) = the normalised mass of row r of probs [rows][nb]
+// (unnormalised masses on `borders` [nb + 1]) between edges[c] and edges[c + 1]; NaN rows for a
+// total that is not positive and finite.  launch_pair_accumulate: window row r (of `rows`; w
+// [rows][G], theta [rows][ldt]) is row r0 + r of the call and belongs to observation (r0 + r) /
+// per; q = llrint(w * 2^40) is ADDED to cellQ [U][G] and, per earlier dimension j < n_prev whose
+// draw theta[r][j] has a cell a on edges [n_prev][G + 1], to pairQ [U][n_prev][G][G] at [a][c];
+// a NaN row raises bad[u] instead.  Integer sums: any order of windows, bitwise the same.
+// launch_pair_final: out[u * ldo + i] = Q[u][i] / (2^40 per) for i < inner, NaN where bad[u].
+// pair_check_cells: NPFN_EINVAL (message starting `who`) unless 2 <= n_cells <= 128 and per <= 2^22.
+constexpr int64_t kPairMaxPer = (int64_t)1 << 22;
+int cell_mass_max_bars();
+int pair_check_cells(int32_t n_cells, int64_t per, const char* who);
+void launch_bar_cell_mass(const float* probs, const float* borders, int64_t rows, int nb, const float* edges, int G,
+                          double* w, hipStream_t s);
+void launch_pair_accumulate(const double* w, const float* theta, int64_t ldt, int n_prev, const float* edges, int G,
+                            int64_t r0, int64_t rows, int64_t per, int64_t* pairQ, int64_t* cellQ, int32_t* bad,
+                            hipStream_t s);
+void launch_pair_final(const int64_t* Q, const int32_t* bad, int64_t n_unique, int64_t inner, int64_t per, float* out,
+                       int64_t ldo, hipStream_t s);
 // dst[r][dst_col0 + c] = src[r / per][c] (per = 1: a plain column copy; per > 1: rows repeated
 // obs-major, as x.repeat_interleave(per, 0))
 void launch_copy_cols(const float* src, int64_t lds, float* dst, int64_t ldd, int64_t rows, int cols,

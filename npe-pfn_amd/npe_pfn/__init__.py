@@ -11,6 +11,7 @@ from npe_pfn.diagnostics import (CoverageRanks, bar_cdf, expected_coverage, pit_
                                  rank_ks_statistic)
 from npe_pfn.marginals import PosteriorMarginals
 from npe_pfn.npe_pfn import NPE_PFN_Core, TabPFN_Based_NPE_PFN, TabPFN_Based_Uncond_Estimator
+from npe_pfn.pair_marginals import PosteriorPairMarginals
 from npe_pfn.restricted_prior import NPE_PFN_RestrictedPrior
 from npe_pfn.tsnpe_pfn import run_tsnpe_pfn
 
@@ -19,6 +20,7 @@ __all__ = [
     "NPE_PFN_Core",
     "NPE_PFN_RestrictedPrior",
     "PosteriorMarginals",
+    "PosteriorPairMarginals",
     "TabPFN_Based_NPE_PFN",
     "TabPFN_Based_Uncond_Estimator",
     "bar_cdf",

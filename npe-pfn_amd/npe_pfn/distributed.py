@@ -422,6 +422,18 @@ def marginals_single_rank(posterior, x: Tensor, group=None, **kwargs):
     return posterior.marginals(x, **kwargs)
 
 
+def pair_marginals_single_rank(posterior, x: Tensor, group=None, **kwargs):
+    """``posterior.pair_marginals(x, ...)`` inside a process group of ONE rank.  The call is not
+    sharded, for :func:`marginals_single_rank`'s reason: every rank would fold its own draws, and
+    combining the per-rank tables needs a weighted reduction that is not provided."""
+    _, world = _rank_world(group)
+    if world > 1:
+        raise NotImplementedError(f"pair_marginals is single-GPU: the process group has {world} ranks; call "
+                                  "posterior.pair_marginals(x) on one rank (multi-GPU sharding of the call is not "
+                                  "provided)")
+    return posterior.pair_marginals(x, **kwargs)
+
+
 def sample_replicas(posterior, x: Tensor, n: int, group=None, **kwargs) -> Tensor:
     """Weak-scaling replicas: every rank draws ``n`` samples of the same observation; ``[world*n, dθ]``."""
     s = posterior.sample((n,), x=x, **kwargs)

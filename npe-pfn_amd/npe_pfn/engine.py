@@ -94,6 +94,8 @@ SIGNATURES = {
                                                _f, _vp]),
     "npfn_ar_marginals": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _i64, _u64, _i64, _vp, _vp, _f,
                                          _vp, _vp, _vp]),
+    "npfn_ar_pair_marginals": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _i64, _u64, _i64, _vp, _vp,
+                                              _f, _vp, _i32, _vp, _vp, _vp]),
     "npfn_ar_log_prob": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _f, _vp]),
     "npfn_ar_log_prob_repeated": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _f, _vp]),
     "npfn_ar_score": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _f, _vp]),
@@ -104,6 +106,9 @@ SIGNATURES = {
     "npfn_restricted_box_round": (ctypes.c_int, [_vp, _vp, _vp, _i32, _f, _i64, _u64, _u64, _i64, _vp, _i64, _vp,
                                                  _vp]),
     "npfn_rank_accumulate": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "npfn_bar_cell_mass": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp]),
+    "npfn_pair_accumulate": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _i32, _i64, _i64, _i64, _vp, _vp,
+                                            ctypes.POINTER(_i32), _vp]),
     "npfn_filter_stdeuclid": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i64, _vp, _vp]),
     "npfn_sir_select": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _u64, _u64, _i64, _vp, _i32, _vp, _vp, _vp, _vp]),
     "npfn_kmeans_fit": (ctypes.c_int, [_vp, _i64, _i32, _i32, _u64, _i32, _f, _vp, _vp, _vp, _vp, _vp]),
@@ -491,6 +496,47 @@ class Engine:
         self.n_features = dx + dth - 1
         return theta, lp, probs, borders
 
+    def ar_pair_marginals(self, x_ctx, theta_ctx, x_unique, n_rows: int, counter: int, edges,
+                          with_log_prob: bool = False, eps: float = 1e-15, row_base: int = 0):
+        """npfn_ar_pair_marginals: :meth:`ar_sample` over ``x_unique.repeat_interleave(n_rows // U,
+        0)`` that also folds every step's row mixtures into 2-D marginals on the cells of ``edges``
+        [dim_theta, G + 1] (row k strictly increasing; see :func:`npe_pfn.pair_marginals.grid_edges`).
+        Returns ``(theta [n_rows, dim_theta], log_prob [n_rows] or None, pair [U, n_pairs, G, G],
+        cell [U, dim_theta, G])`` on the device; ``theta`` and ``log_prob`` are bit for bit those
+        of :meth:`ar_sample` with the same counter and row_base.  ``pair[u, k (k - 1) / 2 + j, a,
+        c]``, j < k, is the mass of (theta_j in cell a, theta_k in cell c) given ``x_unique[u]``;
+        ``cell[u, k, c]`` the mass of theta_k in cell c."""
+        self.full_range()
+        x_ctx = _dev_f32(x_ctx, self.device)
+        theta_ctx = _dev_f32(theta_ctx, self.device)
+        x_unique = _dev_f32(x_unique, self.device)
+        edges = _dev_f32(edges, self.device)
+        if x_ctx.ndim != 2 or theta_ctx.ndim != 2 or theta_ctx.shape[0] != x_ctx.shape[0]:
+            raise ValueError(f"ar_pair_marginals: x_ctx {tuple(x_ctx.shape)} and theta_ctx {tuple(theta_ctx.shape)} "
+                             "do not match")
+        n, dx = x_ctx.shape
+        dth = theta_ctx.shape[1]
+        N = int(n_rows)
+        U = x_unique.shape[0] if x_unique.ndim == 2 else 0
+        if x_unique.ndim != 2 or x_unique.shape[1] != dx or U < 1 or N < U or N % U:
+            raise ValueError(f"ar_pair_marginals: x_unique {tuple(x_unique.shape)} does not repeat into {N} rows of "
+                             f"{dx}")
+        if edges.ndim != 2 or edges.shape[0] != dth or not bool((edges[:, 1:] > edges[:, :-1]).all()):
+            raise ValueError(f"ar_pair_marginals: edges {tuple(edges.shape)} must be [{dth}, G + 1] with strictly "
+                             "increasing rows")
+        G = edges.shape[1] - 1
+        self.check_table(n, dx + dth - 1)
+        theta = torch.empty((N, dth), dtype=torch.float32, device=self.device)
+        lp = torch.empty(N, dtype=torch.float32, device=self.device) if with_log_prob else None
+        pair = torch.empty((U, dth * (dth - 1) // 2, G, G), dtype=torch.float32, device=self.device)
+        cell = torch.empty((U, dth, G), dtype=torch.float32, device=self.device)
+        _check(self.lib, self.lib.npfn_ar_pair_marginals(
+            self.h, _ptr(x_ctx), _ptr(theta_ctx), n, dx, dth, _ptr(x_unique), U, N, int(counter), int(row_base),
+            _ptr(theta), _ptr(lp), float(eps), _ptr(edges), G, _ptr(pair), _ptr(cell), self.stream),
+            "npfn_ar_pair_marginals")
+        self.n_features = dx + dth - 1
+        return theta, lp, pair, cell
+
     def ar_log_prob(self, x_ctx, theta_ctx, x_query, theta, eps: float = 1e-15,
                     x_unique: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``x_unique``: the distinct rows ``x_query`` repeats (as in :meth:`ar_sample`)."""
@@ -683,6 +729,70 @@ class Engine:
         _check(self.lib, self.lib.npfn_rank_accumulate(_ptr(theta), _ptr(logp), _ptr(take), n_obs, per, dim,
                                                        _ptr(theta_true), _ptr(logp_true), _ptr(ref), _ptr(inv_scale),
                                                        _ptr(counts), self.stream), "npfn_rank_accumulate")
+
+    # ------------------------------------------------- pair marginals (npfn_pairs.hip)
+    def bar_cell_mass(self, probs, borders, edges) -> torch.Tensor:
+        """npfn_bar_cell_mass: the normalised mass of every row of ``probs`` [N, n_bars]
+        (unnormalised fp32 bar masses on ``borders`` [n_bars + 1]) in the G cells between
+        ``edges`` [G + 1] (strictly increasing): float64 [N, G] on the device; a row without a
+        positive finite total is NaN."""
+        probs = _dev_f32(probs, self.device)
+        borders = _dev_f32(borders, self.device)
+        edges = _dev_f32(edges, self.device)
+        if probs.ndim != 2 or borders.shape != (probs.shape[1] + 1,) or edges.ndim != 1 or edges.shape[0] < 2:
+            raise ValueError(f"bar_cell_mass: probs {tuple(probs.shape)}, borders {tuple(borders.shape)} and edges "
+                             f"{tuple(edges.shape)} do not match")
+        if not bool((edges[1:] > edges[:-1]).all()):
+            raise ValueError("bar_cell_mass: edges must be strictly increasing")
+        G = edges.shape[0] - 1
+        out = torch.empty((probs.shape[0], G), dtype=torch.float64, device=self.device)
+        _check(self.lib, self.lib.npfn_bar_cell_mass(_ptr(probs), _ptr(borders), probs.shape[0], probs.shape[1],
+                                                     _ptr(edges), G, _ptr(out), self.stream), "npfn_bar_cell_mass")
+        return out
+
+    def pair_accumulate(self, w, theta, edges, r0: int, per: int, pairQ: torch.Tensor, cellQ: torch.Tensor,
+                        bad: torch.Tensor) -> None:
+        """npfn_pair_accumulate: adds one window of cell masses ``w`` [n, G] (float64) to the integer
+        tables ``pairQ`` [U, n_prev, G, G] and ``cellQ`` [U, G] (int64) and raises ``bad`` [U]
+        (int32) -- all on the engine's device, updated in place, zeroed by the caller before the
+        first window.  Window row r is row ``r0 + r`` of the call and belongs to observation
+        ``(r0 + r) // per``; ``theta`` [n, >= n_prev] holds the rows' earlier draws, ``edges``
+        [n_prev, G + 1] their cell borders (``theta`` and ``edges`` may be None: n_prev = 0, only
+        ``cellQ`` is added to).  The definition of every sum:
+        :func:`npe_pfn.pair_marginals.pair_accumulate_host`, which this equals exactly.
+        ValueError for shapes that do not match, before the C call."""
+        r0, per = int(r0), int(per)
+        w = torch.as_tensor(w).to(device=self.device, dtype=torch.float64).contiguous()
+        if w.ndim != 2:
+            raise ValueError(f"pair_accumulate: w {tuple(w.shape)} is not [n, G]")
+        n, G = w.shape
+        n_prev, ldt = 0, 0
+        if (theta is None) != (edges is None):
+            raise ValueError("pair_accumulate: theta and edges are given together")
+        if edges is not None:
+            edges = _dev_f32(edges, self.device)
+            theta = _dev_f32(theta, self.device)
+            if edges.ndim != 2 or edges.shape[1] != G + 1 or theta.ndim != 2 or theta.shape[0] != n \
+                    or theta.shape[1] < edges.shape[0]:
+                raise ValueError(f"pair_accumulate: theta {tuple(theta.shape)} / edges {tuple(edges.shape)} do not "
+                                 f"match {n} rows of {G} cells")
+            if not bool((edges[:, 1:] > edges[:, :-1]).all()):
+                raise ValueError("pair_accumulate: every row of edges must be strictly increasing")
+            n_prev, ldt = edges.shape[0], theta.shape[1]
+        if per < 1 or r0 < 0:
+            raise ValueError(f"pair_accumulate: need per >= 1 and r0 >= 0, got {per} and {r0}")
+        U = cellQ.shape[0] if isinstance(cellQ, torch.Tensor) and cellQ.ndim == 2 else -1
+        for name, t, shape, dt in (("pairQ", pairQ, (U, n_prev, G, G), torch.int64), ("cellQ", cellQ, (U, G), torch.int64),
+                                   ("bad", bad, (U,), torch.int32)):
+            if (not isinstance(t, torch.Tensor) or t.dtype != dt or t.device != self.device or not t.is_contiguous()
+                    or tuple(t.shape) != shape):
+                raise ValueError(f"pair_accumulate: {name} must be a contiguous {dt} {list(shape)} tensor on the "
+                                 "engine's device")
+        if n and (r0 + n - 1) // per >= U:
+            raise ValueError(f"pair_accumulate: rows {r0}..{r0 + n - 1} of {per} per observation exceed {U} observations")
+        _check(self.lib, self.lib.npfn_pair_accumulate(
+            _ptr(w), _ptr(theta), ldt, n_prev, _ptr(edges), G, r0, n, per, _ptr(pairQ), _ptr(cellQ),
+            ctypes.cast(ctypes.c_void_p(bad.data_ptr()), ctypes.POINTER(_i32)), self.stream), "npfn_pair_accumulate")
 
     def filter_stdeuclid(self, x: torch.Tensor, obs: torch.Tensor, k: int) -> torch.Tensor:
         x = _dev_f32(x, self.device)

@@ -32,6 +32,8 @@ from .accept_reject_sampler import accept_reject_sample
 from .diagnostics import CoverageRanks, bar_cdf, rank_accumulate_host
 from .kmeans import KMeansState
 from .marginals import PosteriorMarginals
+from .pair_marginals import MAX_PER as PAIR_MAX_PER
+from .pair_marginals import PosteriorPairMarginals, grid_edges, pair_accumulate_host, tables_from_sums
 from .support_posterior import (get_filtering_method, latest_filtering, no_filtering,
                                 standardized_euclidean_filtering)
 from .tabpfn import TabPFNClassifier, TabPFNRegressor
@@ -623,6 +625,101 @@ class NPE_PFN_Core:
             feats = torch.cat([feats, draw[:, None].to(feats.device)], dim=1)
         return feats[:, dx:], torch.stack(probs, 1), torch.stack(borders, 0)
 
+    def pair_marginals(self, x: Tensor, num_draws: int = 10_000, bins: int = 64, limits=None,
+                       max_sampling_batch_size: int = 10_000, return_samples: bool = False) -> PosteriorPairMarginals:
+        """2-D posterior marginals of every pair of parameters on a grid of ``bins`` x ``bins`` cells
+        (what a corner plot draws), folded from the conditionals of ``num_draws`` sampler draws per
+        observation: for a pair (j, k), j < k, the earlier parameter enters through the draw's
+        cell, the later one through the cell masses of the full predictive distribution theta_k
+        was drawn from ("half Rao-Blackwellised"; no extra forward pass).  See
+        :mod:`npe_pfn.pair_marginals`.
+
+        ``x``, the contexts, ``max_sampling_batch_size``, counters and Philox rows are those of
+        :meth:`marginals`; the calls' tables are combined on the host in fp64, weighted by their
+        draws.  ``limits`` [d_theta, 2] are the outer edges of the grid: by default the box prior's
+        bounds when the prior is a box, else the per-dimension min / max of the call's context
+        thetas.  The edges are ``lo + (hi - lo) * c / bins`` in fp64 rounded to fp32, the last one
+        exactly ``hi``; ValueError for a degenerate or non-finite limit or ``bins`` outside 2..128.
+        Mass outside the limits is not in the tables (``mass_inside``); nothing is truncated to
+        the prior's support or reweighted.  ``return_samples=True`` keeps the draws as ``samples``
+        [M, num_draws, d_theta].  Results live on the sampler's device."""
+        x = self._validate_x(self._embed(x) if self.embedding_net else x)
+        num_draws, cap = int(num_draws), int(max_sampling_batch_size)
+        n_obs = x.shape[0]
+        if num_draws < 1 or cap < 1:
+            raise ValueError(f"pair_marginals: num_draws ({num_draws}) and max_sampling_batch_size ({cap}) must be "
+                             ">= 1")
+        if n_obs == 1:
+            theta_ctx, x_ctx = self.get_context(x)
+        else:
+            theta_ctx, x_ctx = self._theta_train, self._x_train
+        d = theta_ctx.shape[1]
+        if limits is None:
+            bounds = _box_bounds(self.prior) if self.prior is not None else None
+            if bounds is not None:
+                limits = torch.stack([bounds[0].detach().reshape(-1), bounds[1].detach().reshape(-1)], 1)
+            else:
+                limits = torch.stack([theta_ctx.min(0).values, theta_ctx.max(0).values], 1)
+        limits = torch.as_tensor(limits)
+        if tuple(limits.shape) != (d, 2):
+            raise ValueError(f"pair_marginals: limits must be [{d}, 2], got {tuple(limits.shape)}")
+        edges = grid_edges(limits.cpu(), bins).to(x.device)
+        per_call = max(1, min(cap // n_obs, PAIR_MAX_PER))
+        acc_pair = acc_cell = None
+        draws = []
+        done = 0
+        with self._reuse_fits():
+            while done < num_draws:
+                n = min(per_call, num_draws - done)
+                # an observation shard of a larger batch draws at the unsharded batch's Philox rows
+                rb = self._obs_offset * n if n_obs > 1 else 0
+                if hasattr(self._model, "ar_pair_marginals"):
+                    th, _, pair, cell = self._model.ar_pair_marginals(x_ctx, theta_ctx, x, n_obs * n, edges,
+                                                                      row_base=rb)
+                else:
+                    th, pair, cell = self._pair_marginals_generic(x_ctx, theta_ctx, x, n, edges)
+                pair, cell = pair.to(torch.float64) * n, cell.to(torch.float64) * n
+                acc_pair = pair if acc_pair is None else acc_pair + pair
+                acc_cell = cell if acc_cell is None else acc_cell + cell
+                if return_samples:
+                    draws.append(th.reshape(n_obs, n, -1))
+                done += n
+        return PosteriorPairMarginals((acc_pair / num_draws).to(torch.float32), (acc_cell / num_draws).to(torch.float32),
+                                      edges.to(acc_pair.device), num_draws,
+                                      samples=torch.cat(draws, 1) if return_samples else None)
+
+    def _pair_marginals_generic(self, x_ctx: Tensor, theta_ctx: Tensor, x: Tensor, per: int, edges: Tensor):
+        """:meth:`_ar_generic` over ``x`` repeated obs-major ``per`` times, with every step's
+        predictive distributions (fp64 softmax of the full logits) re-binned onto ``edges`` --
+        cell masses from :func:`npe_pfn.diagnostics.bar_cdf` differences -- and folded by
+        :func:`pair_accumulate_host`: (theta [M * per, d_theta], pair [M, n_pairs, G, G], cell [M,
+        d_theta, G]), the tables fp32 as the engine's."""
+        joint = torch.cat([x_ctx, theta_ctx], dim=1)
+        dx, d = x_ctx.shape[1], theta_ctx.shape[1]
+        n_obs, G = x.shape[0], edges.shape[1] - 1
+        feats = x.repeat_interleave(per, dim=0)
+        pairs, cells = [], []
+        for k in range(d):
+            self._model.fit(joint[:, : dx + k], joint[:, dx + k])
+            pred = self._model.predict(feats, output_type="full", quantiles=[])
+            draw = pred["criterion"].sample(pred["logits"])
+            logits = torch.as_tensor(pred["logits"])
+            dev = logits.device
+            ones = torch.ones(logits.shape[0], dtype=torch.float64, device=dev)
+            F = torch.stack([bar_cdf(logits, pred["criterion"].borders, ones * float(e)) for e in edges[k].tolist()], 1)
+            w = (F[:, 1:] - F[:, :-1]).clamp(min=0.0)
+            pairQ = torch.zeros((n_obs, k, G, G), dtype=torch.int64, device=dev)
+            cellQ = torch.zeros((n_obs, G), dtype=torch.int64, device=dev)
+            bad = torch.zeros(n_obs, dtype=torch.int32, device=dev)
+            pair_accumulate_host(w, feats[:, dx:] if k else None, edges[:k] if k else None, 0, per, pairQ, cellQ, bad)
+            if k:
+                pairs.append(tables_from_sums(pairQ, bad, per))
+            cells.append(tables_from_sums(cellQ, bad, per))
+            feats = torch.cat([feats, draw[:, None].to(feats.device)], dim=1)
+        dev = cells[0].device
+        pair = torch.cat(pairs, 1) if pairs else torch.zeros((n_obs, 0, G, G), dtype=torch.float32, device=dev)
+        return feats[:, dx:], pair, torch.stack(cells, 1)
+
     def _score_batched(self, theta: Tensor, x: Tensor, eps: float, want_logp: bool, want_cdf: bool):
         """(summed log density [...], per-step log densities [..., d_theta], PIT [..., d_theta]) of
         one teacher-forced pass over the full table; entries not asked for are None."""
@@ -960,6 +1057,35 @@ class TabPFN_Based_Uncond_Estimator(NPE_PFN_Core):
         the mixture's marginal is not a column average on one grid."""
         raise NotImplementedError("TabPFN_Based_Uncond_Estimator.marginals: the clusters' bar borders differ, so "
                                   "their mixtures do not average on one grid")
+
+    def pair_marginals(self, num_draws: int = 10_000, bins: int = 64, limits=None,
+                       max_sampling_batch_size: int = 10_000, return_samples: bool = False) -> PosteriorPairMarginals:
+        """2-D marginals of the mixture (:meth:`NPE_PFN_Core.pair_marginals`): every cluster folds
+        ``num_draws`` draws of its own sampler -- on its own context, given one dummy x ~ N(0, 1)
+        -- onto the SAME cell edges, and the clusters' tables are mixed with the weights ``counts_c
+        / n`` in fp64.  The clusters' bar borders differ, but a common coarse grid does not care.
+        ``limits`` default to the per-dimension min / max of all training thetas.  ``samples``
+        (when asked for) are [1, num_clusters * num_draws, d_theta], cluster after cluster (NOT
+        draws of the mixture: every cluster contributes ``num_draws``)."""
+        if limits is None:
+            limits = torch.stack([self._theta_train.min(0).values, self._theta_train.max(0).values], 1)
+        weights = self.counts / self.counts.sum()
+        pair = cell = edges = None
+        draws = []
+        try:
+            for c in range(self.num_clusters):
+                self.set_cluster_state(c)
+                pm = super().pair_marginals(torch.randn(1, 1).to(self._theta_train.device), num_draws, bins, limits,
+                                            max_sampling_batch_size, return_samples)
+                wp, wc = pm.probs.to(torch.float64) * float(weights[c]), pm.marginal_probs.to(torch.float64) * float(weights[c])
+                pair = wp if pair is None else pair + wp
+                cell = wc if cell is None else cell + wc
+                edges = pm.edges
+                draws.append(pm.samples)
+        finally:
+            self.set_cluster_state()
+        return PosteriorPairMarginals(pair.to(torch.float32), cell.to(torch.float32), edges, int(num_draws),
+                                      samples=torch.cat(draws, 1) if return_samples else None)
 
     def pit_batched(self, theta: Tensor, x: Tensor = None) -> Tensor:
         """Not provided, for the reason given at :meth:`log_prob_batched`."""

@@ -288,6 +288,17 @@ class TabPFNRegressor:
         return self.engine.ar_marginals(x_ctx, theta_ctx, x_unique, n_rows, counter, with_log_prob, eps,
                                         row_base=row_base)
 
+    def ar_pair_marginals(self, x_ctx, theta_ctx, x_unique, n_rows: int, edges, with_log_prob: bool = False,
+                          eps: float = 1e-15, row_base: int = 0):
+        """:meth:`ar_sample` over ``x_unique`` repeated obs-major into ``n_rows`` query rows, with the
+        2-D marginals of every pair of parameters on the cells of ``edges`` (Engine.ar_pair_marginals):
+        ``(theta, log_prob, pair, cell)``.  Advances the sample counter exactly as :meth:`ar_sample` does."""
+        _check_table(len(x_ctx), x_ctx.shape[1] + theta_ctx.shape[1] - 1, self.ignore_pretraining_limits)
+        counter = self.sample_counter
+        self.sample_counter += int(theta_ctx.shape[1])
+        return self.engine.ar_pair_marginals(x_ctx, theta_ctx, x_unique, n_rows, counter, edges, with_log_prob, eps,
+                                             row_base=row_base)
+
     def ar_log_prob(self, x_ctx, theta_ctx, x_query, theta, eps: float = 1e-15, x_unique=None):
         _check_table(len(x_ctx), x_ctx.shape[1] + theta_ctx.shape[1] - 1, self.ignore_pretraining_limits)
         return self.engine.ar_log_prob(x_ctx, theta_ctx, x_query, theta, eps, x_unique=x_unique)
