@@ -550,6 +550,13 @@ int npfn_set_estimator_set(npfn_engine* h, int32_t e0, int32_t count, int32_t st
 int npfn_forward_targets(npfn_engine* h, const float* Xq, int64_t ldq, int64_t n_rows, void* tokens_out,
                          void* stream);
 
+/* The same forward plus the decoder head, before the ensemble mix: logits_out (fp16,
+ * [count][n_rows][n_bars]) = the decoder logits of every (estimator, row) of the estimator
+ * range, as npfn_predict's mix reads them.  Works under a partial range (nothing is mixed):
+ * the per-estimator view for tests and diagnostics. */
+int npfn_forward_logits(npfn_engine* h, const float* Xq, int64_t ldq, int64_t n_rows, void* logits_out,
+                        void* stream);
+
 /* Decoder head + ensemble mix + criterion.sample (+ NLL) of one autoregressive step
  * (npe_pfn.py:143-159) from the target tokens of ALL estimators: tokens (bf16,
  * [n_est][n_rows][192], n_est = cfg.n_estimators).  theta_out [n_rows]; row i draws

@@ -2030,6 +2030,27 @@ int npfn_forward_targets(npfn_engine* h, const float* Xq, int64_t ldq, int64_t n
   return NPFN_OK;
 }
 
+int npfn_forward_logits(npfn_engine* h, const float* Xq, int64_t ldq, int64_t n_rows, void* logits_out,
+                        void* stream) {
+  RCHK(check_engine(h));
+  if (!h->f->fitted || h->f->ncls > 0) return fail(NPFN_ESTATE, "forward_logits before a regressor fit");
+  if (!Xq || !logits_out) return fail(NPFN_EINVAL, "forward_logits: null pointer");
+  if (ldq < h->f->F) return fail(NPFN_EINVAL, "forward_logits: ldq < n_features");
+  if (n_rows < 0) return fail(NPFN_EINVAL, "forward_logits: negative n_rows");
+  hipStream_t s = (hipStream_t)stream;
+  const int nb = h->cfg.n_bars;
+  logit_t* out = (logit_t*)logits_out;
+  for (int64_t r0 = 0; r0 < n_rows; r0 += h->chunk_rows) {
+    const int64_t rows = std::min(h->chunk_rows, n_rows - r0);
+    RCHK(predict_logits_chunk(h, Xq + r0 * ldq, ldq, rows, s));
+    for (int e = 0; e < h->ne; ++e)
+      HIPCHK(hipMemcpyAsync(out + ((size_t)e * n_rows + r0) * nb, (const logit_t*)h->logits.p + (size_t)e * rows * nb,
+                            (size_t)rows * nb * sizeof(logit_t), hipMemcpyDeviceToDevice, s));
+  }
+  HIPCHK(hipGetLastError());
+  return NPFN_OK;
+}
+
 int npfn_head_sample(npfn_engine* h, const void* tokens, int32_t n_est, int64_t n_rows, uint64_t counter,
                      int64_t row_base, float* theta_out, float* log_prob_acc, float eps, void* stream) {
   RCHK(check_engine(h));

@@ -116,6 +116,7 @@ SIGNATURES = {
     "npfn_set_estimator_range": (ctypes.c_int, [_vp, _i32, _i32]),
     "npfn_set_estimator_set": (ctypes.c_int, [_vp, _i32, _i32, _i32]),
     "npfn_forward_targets": (ctypes.c_int, [_vp, _vp, _i64, _i64, _vp, _vp]),
+    "npfn_forward_logits": (ctypes.c_int, [_vp, _vp, _i64, _i64, _vp, _vp]),
     "npfn_head_sample": (ctypes.c_int, [_vp, _vp, _i32, _i64, _u64, _i64, _vp, _vp, _f, _vp]),
     "npfn_ar_fit_begin": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp]),
     "npfn_ar_fit_step": (ctypes.c_int, [_vp, _i32, _vp]),
@@ -861,6 +862,19 @@ class Engine:
                           dtype=torch.bfloat16, device=self.device)
         _check(self.lib, self.lib.npfn_forward_targets(self.h, _ptr(Xq), Xq.shape[1], Xq.shape[0], _ptr(out),
                                                        self.stream), "npfn_forward_targets")
+        return out
+
+    def forward_logits(self, Xq) -> torch.Tensor:
+        """[count, N, n_bars] fp16 decoder logits of this engine's estimators, before the ensemble
+        mix (npfn_forward_logits; a partial estimator range is fine)."""
+        if self.n_features is None:
+            raise EngineError("forward_logits before fit")
+        Xq = _dev_f32(Xq, self.device)
+        if Xq.ndim != 2 or Xq.shape[1] != self.n_features:
+            raise ValueError(f"forward_logits: X has shape {tuple(Xq.shape)}, fit had {self.n_features} features")
+        out = torch.empty((self.ne, Xq.shape[0], self.cfg.n_bars), dtype=torch.float16, device=self.device)
+        _check(self.lib, self.lib.npfn_forward_logits(self.h, _ptr(Xq), Xq.shape[1], Xq.shape[0], _ptr(out),
+                                                      self.stream), "npfn_forward_logits")
         return out
 
     def head_sample(self, tokens: torch.Tensor, counter: int, row_base: int = 0,

@@ -469,8 +469,14 @@ class OracleTabPFN:
         return out.reshape(x.shape)
 
     # ---------------------------------------------------------------- predict
-    def _estimator_logits(self, Xq: np.ndarray) -> np.ndarray:
-        """Decoder logits [E, R, n_out] of every estimator for the query rows."""
+    def target_tokens(self, Xq: np.ndarray) -> np.ndarray:
+        """Decoder-input tokens [E, R, d] (float32): the last layer's target token of every
+        (estimator, query row), rounded to bf16 when emulating -- the engine's
+        npfn_forward_targets."""
+        return np.concatenate(self._target_token_groups(Xq), 0)
+
+    def _target_token_groups(self, Xq: np.ndarray) -> List[np.ndarray]:
+        """target_tokens per estimator group (_groups): [E_g, R, d] each."""
         st = self.state
         assert st is not None, "fit() first"
         Xq = np.asarray(Xq, dtype=np.float32)
@@ -480,13 +486,21 @@ class OracleTabPFN:
             x = np.stack([self._encode_one(Xq, st, e, train_y=None, train=False) for e in range(a, b)])
             for l in range(self.L):
                 x = self._layer(x, l, st.kv[g])
-            z = x[:, :, st.estimators[a].n_groups, :]              # target token [Eg, R, d]
-            h = self._bf(self._gelu(self._mm(z, "dec_w1") + self.w["dec_b1"]))
-            lg = (self._mm(h, "dec_w2") + self.w["dec_b2"]).astype(np.float32)
-            if self.emulate:  # the engine stores the decoder logits as fp16 (npfn_kernels.h logit_t)
-                lg = lg.astype(np.float16).astype(np.float32)
-            out.append(lg)
-        return np.concatenate(out, 0)
+            out.append(self._bf(x[:, :, st.estimators[a].n_groups, :]))   # target token [Eg, R, d]
+        return out
+
+    def decode_tokens(self, z: np.ndarray) -> np.ndarray:
+        """Decoder logits [..., n_out] of decoder-input tokens z [..., d]."""
+        h = self._bf(self._gelu(self._mm(z, "dec_w1") + self.w["dec_b1"]))
+        lg = (self._mm(h, "dec_w2") + self.w["dec_b2"]).astype(np.float32)
+        if self.emulate:  # the engine stores the decoder logits as fp16 (npfn_kernels.h logit_t)
+            lg = lg.astype(np.float16).astype(np.float32)
+        return lg
+
+    def _estimator_logits(self, Xq: np.ndarray) -> np.ndarray:
+        """Decoder logits [E, R, n_out] of every estimator for the query rows."""
+        # decoded group by group, as before target_tokens existed: the same GEMM shapes, the same bits
+        return np.concatenate([self.decode_tokens(z) for z in self._target_token_groups(Xq)], 0)
 
     def predict_probs(self, Xq: np.ndarray, return_estimator_logits: bool = False):
         """Ensemble-mean bar probabilities [R, n_bars] over the common borders: per estimator
