@@ -585,8 +585,39 @@ int npfn_ar_fit_step(npfn_engine* h, int32_t k, void* stream);
  * the next call with the same token, context shape, mode and estimator range uses them
  * instead of refitting.  The caller promises that the context (x_ctx, theta_ctx) is the
  * same for all calls under one token -- e.g. one token per sample() call.  0 (default)
- * refits every call.  npfn_fit / npfn_fit_classes never touch the cached fits. */
+ * refits every call.  npfn_fit / npfn_fit_classes never touch the cached fits.
+ * Under a NEW non-zero token the fits are looked up in the fit cache (below) before anything
+ * is refitted. */
 int npfn_set_fit_token(npfn_engine* h, uint64_t token);
+
+/* Fit cache: the per-step fits outlive their token.  Unlike the reference, which refits at
+ * every step of every call, the engine refits only when the context table or a fit-relevant
+ * setting has changed.  A cached set holds the fits of every AR step of one context table:
+ * per step the preprocessing fits, the preprocessed train table and the train-side K/V cache
+ * (n_layers * sum_e C_e * 6 * ntile * 2048 bf16 values; about 1 GB per step and 10 GB per set
+ * at 1000 context rows, 10 + 10 columns and 8 estimators), plus the engine's own copy of the
+ * table (n_ctx * (dim_x + dim_theta) floats).
+ * The first npfn_ar_* / npfn_ar_fit_begin call under a new non-zero token compares its context
+ * with the cached sets whose key is equal -- the key is (n_ctx, dim_x, dim_theta, the
+ * preprocessing mode with its regressor / classifier pipelines and quantile divisor, the
+ * estimator set) -- over the full content, on the 32-bit patterns (a table with NaN cells can
+ * hit; +0 and -0 differ), never by address: one small kernel, one copy of a flag per candidate
+ * back to the host and one synchronize of `stream`.  On a hit the set's fitted steps are used
+ * as they are and only steps it does not hold yet are fitted; on a miss a free set, or the
+ * least recently used one, is refitted.  The results are bit for bit those of a refit.
+ * Calls on different streams are ordered by events inside the engine; the stepwise readers
+ * (npfn_forward_targets / npfn_head_sample after npfn_ar_fit_step) are not, and stay on one
+ * stream.  npfn_set_preprocessing and a switch between the regressor's and the classifier's
+ * pipelines forget every cached fit; npfn_set_estimator_set keeps them (the set is in the key).
+ * max_sets: sets kept (default 1: the memory one call holds anyway; 0: no reuse across tokens);
+ * max_bytes: device memory of all sets, 0 = no limit (default) -- when a call leaves more than
+ * that resident, least recently used sets are freed, down to one. */
+int npfn_set_fit_cache(npfn_engine* h, int32_t max_sets, uint64_t max_bytes);
+/* Lookups under new tokens that hit / missed since creation, sets that hold fits, and the device
+ * memory of all sets.  Any pointer may be NULL. */
+int npfn_fit_cache_stats(npfn_engine* h, uint64_t* hits, uint64_t* misses, int32_t* sets, uint64_t* bytes);
+/* Frees every cached set (synchronizes with the calls that use them). */
+int npfn_fit_cache_clear(npfn_engine* h);
 
 /* Query rows per forward chunk of npfn_predict / npfn_predict_proba / npfn_ar_sample /
  * npfn_ar_log_prob (default 16384).  The reference runs one `predict` over every query

@@ -14,6 +14,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -129,6 +130,28 @@ struct Fit {
   void release();
 };
 
+// One entry of the fit cache: the per-step fits of one context table under one set of
+// fit-relevant settings.  `key` holds everything a fit reads from the engine besides the table
+// (fit_key), `ctx` the engine's own copy of the table the slots were fitted on; a call under a
+// new fit token adopts the set when key and every 32-bit pattern of the table are equal
+// (begin_ar_fits).  A slot's `fitted` says whether that step's fit is complete: a set may be
+// filled only up to some step (npfn_ar_fit_step).
+constexpr int kFitKey = 9;
+struct FitSet {
+  std::vector<Fit> slots;  // per AR step k: the fit of step k
+  bool valid = false;      // key / ctx describe the slots (false while a miss is being filled)
+  uint64_t token = 0;      // the fit token the set was last used under
+  uint64_t key[kFitKey] = {};
+  DevBuf ctx;              // [n][dim_x + dim_theta] context table of the fits
+  size_t bytes = 0;        // device memory of the slots' buffers and ctx
+  uint64_t stamp = 0;      // LRU clock of the last use
+  // stream order: `ready` follows the fits queued on the caller's stream, ready_side /
+  // ready_train those on the engine's side streams, `last_use` the last call that read the set;
+  // a call that adopts the set on another stream waits for all of them before it reads or
+  // overwrites a slot
+  hipEvent_t ready = nullptr, ready_side = nullptr, ready_train = nullptr, last_use = nullptr;
+};
+
 // Forward workspaces of one stream (token tensors of the rows in flight).
 struct Work {
   DevBuf resid, resid_bf, qkv, attn, hid;
@@ -163,6 +186,10 @@ struct npfn_engine {
   std::vector<hipEvent_t> prep_done;  // per AR step: its fit (preprocessing + train forward) is complete
   std::vector<hipEvent_t> stat_done;  // per AR step: its preprocessing fit is complete
   hipEvent_t setup_done = nullptr;
+  // side_busy: fits were queued on the side streams since the caller's stream last waited for
+  // all of them (order_after_last_call, which records side_idle on side / side_t)
+  hipEvent_t side_idle[2] = {nullptr, nullptr};
+  bool side_busy = false;
   // npfn_ar_fit_begin / npfn_ar_fit_step: the AR fits of a call driven step by step
   bool ar_active = false, ar_piped = false, ar_reuse = false;
   int64_t ar_n = 0;
@@ -171,9 +198,21 @@ struct npfn_engine {
   // per-step fits of an earlier call with the same fit token (npfn_set_fit_token)
   Fit fit0;
   Fit* f = &fit0;
-  std::vector<Fit> slots;      // per AR step k: the fit of step k
   uint64_t fit_token = 0;      // npfn_set_fit_token
-  uint64_t slot_key[6] = {0, 0, 0, 0, 0, 0};  // token, n, dim_x, dim_theta, mode, range of the cached slots
+  // fit cache (npfn_set_fit_cache): the sets of per-step fits kept across calls; `cur` is the
+  // set of the token in use.  max_sets = 0: no reuse across tokens (one set is still kept for
+  // the calls of one token)
+  std::vector<std::unique_ptr<FitSet>> sets;
+  FitSet* cur = nullptr;
+  int max_sets = 1;
+  size_t max_bytes = 0;        // 0: no limit
+  uint64_t lru_clock = 0, cache_hits = 0, cache_misses = 0;
+  int32_t* diff_dev = nullptr;   // [kCtxCopiesMax] mismatch flags of k_ctx_diff
+  int32_t* diff_host = nullptr;  // pinned copy
+  // the caller's stream of the last call under a fit token: a call on another stream waits for
+  // that call (cur->last_use) before it touches the engine's shared workspaces
+  hipStream_t last_stream = nullptr;
+  bool last_stream_set = false;
   // workspaces: the forwards' token tensors per stream (w = the one in use: wmain on the
   // caller's stream, wside for the AR train forwards on side_t)
   Work wmain, wside;
@@ -1105,6 +1144,8 @@ int apply_preprocessing(npfn_engine* h, int mode, bool classifier = false) {
   h->pre_cls = classifier;
   return NPFN_OK;
 }
+void cache_invalidate(npfn_engine* h);
+int order_after_last_call(npfn_engine* h, hipStream_t s);
 // the pipeline assignment of the engine's mode for a regressor (classifier = false) or a
 // classifier fit; mode 3 differs between the two (re-uploaded only on a switch)
 int ensure_pipelines(npfn_engine* h, bool classifier) {
@@ -1112,8 +1153,7 @@ int ensure_pipelines(npfn_engine* h, bool classifier) {
   RCHK(apply_preprocessing(h, 3, classifier));
   h->ar_active = false;  // an AR fit sequence begun under the other pipelines is void (as in the other setters)
   h->ar_reuse = false;
-  for (Fit& sl : h->slots) sl.fitted = false;
-  std::memset(h->slot_key, 0, sizeof(h->slot_key));
+  cache_invalidate(h);
   h->fit0.fitted = false;
   return NPFN_OK;
 }
@@ -1130,6 +1170,7 @@ int ar_common_setup(npfn_engine* h, const float* x_ctx, const float* theta_ctx, 
   if (!x_ctx || !theta_ctx || !xq) return fail(NPFN_EINVAL, "ar: null input");
   if (dx < 1 || dth < 1 || n < 1 || N < 0) return fail(NPFN_EINVAL, "ar: bad dimensions");
   const int Ft = dx + dth;
+  RCHK(order_after_last_call(h, s));
   RCHK(ensure(h->joint, (size_t)n * Ft * sizeof(float), s));
   RCHK(ensure(h->feat, (size_t)std::max<int64_t>(N, 1) * Ft * sizeof(float), s));
   RCHK(ensure(h->logp, (size_t)std::max<int64_t>(N, 1) * sizeof(float), s));
@@ -1140,29 +1181,226 @@ int ar_common_setup(npfn_engine* h, const float* x_ctx, const float* theta_ctx, 
   return NPFN_OK;
 }
 
-// Selects the fit of AR step k (npfn_ar_sample / npfn_ar_log_prob).  Without a fit token:
-// fit0, refitted every call.  With one (npfn_set_fit_token): the per-step slot k, refitted
-// only when the token or the call's shape changed since the slots were filled -- the
-// accept/reject batches of one sample() call share their context (npe_pfn.py:284-292).
-// Returns in `refit` whether step k must be fitted.
-void begin_ar_fits(npfn_engine* h, int64_t n, int dx, int dth, bool& reuse) {
-  const uint64_t key[6] = {h->fit_token, (uint64_t)n, (uint64_t)dx, (uint64_t)dth, (uint64_t)h->pre_mode,
-                           ((uint64_t)h->es << 48) | ((uint64_t)h->e0 << 24) | (uint64_t)h->ne};
-  reuse = h->fit_token != 0 && (int)h->slots.size() >= dth && std::memcmp(key, h->slot_key, sizeof(key)) == 0;
-  if (h->fit_token != 0 && !reuse) {
-    if ((int)h->slots.size() < dth) h->slots.resize(dth);
-    std::memset(h->slot_key, 0, sizeof(h->slot_key));
-    // a slot filled under another token, context or estimator set is not a fit of this call
-    for (Fit& sl : h->slots) sl.fitted = false;
+// ---------------------------------------------------------------- fit cache
+// Everything a fit reads from the engine besides the context table: the table's shape, the
+// preprocessing (mode, regressor / classifier pipelines, quantile divisor) and the estimator
+// set.  The weights, the model configuration and random_state are fixed at creation.
+void fit_key(const npfn_engine* h, int64_t n, int dx, int dth, uint64_t* key) {
+  const uint64_t k[kFitKey] = {(uint64_t)n, (uint64_t)dx, (uint64_t)dth, (uint64_t)h->pre_mode, (uint64_t)h->pre_cls,
+                               (uint64_t)h->qdiv, (uint64_t)h->e0, (uint64_t)h->ne, (uint64_t)h->es};
+  std::memcpy(key, k, sizeof(k));
+}
+size_t set_bytes(const FitSet& fs) {
+  size_t b = fs.ctx.bytes;
+  for (const Fit& f : fs.slots) {
+    const DevBuf* bufs[] = {&f.colstat, &f.ystats, &f.vcol, &f.mu,   &f.sd,   &f.gscale, &f.eF,  &f.kvc,  &f.cperm,   &f.ybar_e,  &f.qtab,
+                            &f.qn,      &f.qstat, &f.qsub,  &f.plam, &f.pstat, &f.svd, &f.svdw, &f.htab,   &f.ylam, &f.ttab, &f.tcancel, &f.tscratch,
+                            &f.tviews};
+    for (const DevBuf* d : bufs) b += d->bytes;
+  }
+  return b;
+}
+bool set_owns(const FitSet& fs, const Fit* f) {
+  return !fs.slots.empty() && f >= fs.slots.data() && f < fs.slots.data() + fs.slots.size();
+}
+// Waits (host) for every stream that may still read or write the set, then frees its memory.
+void set_release(npfn_engine* h, FitSet& fs) {
+  for (hipEvent_t e : {fs.ready, fs.ready_side, fs.ready_train, fs.last_use})
+    if (e) (void)hipEventSynchronize(e);
+  if (set_owns(fs, h->f)) h->f = &h->fit0;
+  for (Fit& f : fs.slots) f.release();
+  free_buf(fs.ctx);
+  fs.valid = false;
+  fs.token = 0;
+  fs.bytes = 0;
+}
+void set_destroy(npfn_engine* h, FitSet& fs) {
+  set_release(h, fs);
+  for (hipEvent_t e : {fs.ready, fs.ready_side, fs.ready_train, fs.last_use})
+    if (e) (void)hipEventDestroy(e);
+  fs.ready = fs.ready_side = fs.ready_train = fs.last_use = nullptr;
+  if (h->cur == &fs) h->cur = nullptr;
+}
+// Forgets every cached fit and keeps the memory (a setting outside the key changed): as a
+// cleared slot key did before the cache.
+void cache_invalidate(npfn_engine* h) {
+  for (auto& fs : h->sets) {
+    fs->valid = false;
+    fs->token = 0;
+    for (Fit& sl : fs->slots) sl.fitted = false;
   }
 }
-void end_ar_fits(npfn_engine* h, int64_t n, int dx, int dth) {
-  if (h->fit_token == 0) return;
-  const uint64_t key[6] = {h->fit_token, (uint64_t)n, (uint64_t)dx, (uint64_t)dth, (uint64_t)h->pre_mode,
-                           ((uint64_t)h->es << 48) | ((uint64_t)h->e0 << 24) | (uint64_t)h->ne};
-  std::memcpy(h->slot_key, key, sizeof(key));
+size_t cache_bytes(const npfn_engine* h) {
+  size_t b = 0;
+  for (auto& fs : h->sets) b += fs->bytes;
+  return b;
 }
-Fit* step_fit(npfn_engine* h, int k) { return h->fit_token != 0 ? &h->slots[k] : &h->fit0; }
+int cache_capacity(const npfn_engine* h) { return std::max(h->max_sets, 1); }
+// Brings the cache within its limits: more sets than allowed are destroyed, and while the byte
+// limit is exceeded the least recently used set other than `keep` gives its memory back, down
+// to one set holding any.
+void cache_enforce(npfn_engine* h, FitSet* keep) {
+  auto lru = [&](bool with_memory) {
+    FitSet* v = nullptr;
+    for (auto& fs : h->sets)
+      if (fs.get() != keep && (!with_memory || fs->bytes > 0) && (!v || fs->stamp < v->stamp)) v = fs.get();
+    return v;
+  };
+  while ((int)h->sets.size() > cache_capacity(h)) {
+    FitSet* v = lru(false);
+    if (!v) break;
+    set_destroy(h, *v);
+    for (size_t i = 0; i < h->sets.size(); ++i)
+      if (h->sets[i].get() == v) {
+        h->sets.erase(h->sets.begin() + i);
+        break;
+      }
+  }
+  while (h->max_bytes > 0 && cache_bytes(h) > h->max_bytes) {
+    FitSet* v = lru(true);
+    if (!v) break;
+    set_release(h, *v);
+  }
+}
+int set_events(FitSet& fs) {
+  for (hipEvent_t* e : {&fs.ready, &fs.ready_side, &fs.ready_train, &fs.last_use})
+    if (!*e) HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+  return NPFN_OK;
+}
+// Before a call rewrites the engine's shared workspaces (the context table, the query
+// features, the forwards' token tensors) on s:
+// * fits queued on the side streams read h->joint; after an npfn_ar_fit_begin whose steps were
+//   not all driven, or a call that failed half way, some may still be pending -- s waits for
+//   everything queued there so far;
+// * a call on another stream than the last one under a fit token waits for that call, whose
+//   last_use follows its last read of the workspaces (end_ar_fits).
+int order_after_last_call(npfn_engine* h, hipStream_t s) {
+  if (h->side_busy) {
+    HIPCHK(hipEventRecord(h->side_idle[0], h->side));
+    HIPCHK(hipEventRecord(h->side_idle[1], h->side_t));
+    HIPCHK(hipStreamWaitEvent(s, h->side_idle[0], 0));
+    HIPCHK(hipStreamWaitEvent(s, h->side_idle[1], 0));
+    h->side_busy = false;
+  }
+  if (h->fit_token != 0 && h->last_stream_set && h->last_stream != s && h->cur && h->cur->last_use)
+    HIPCHK(hipStreamWaitEvent(s, h->cur->last_use, 0));
+  return NPFN_OK;
+}
+
+// Selects the fits of an AR call (npfn_ar_sample / npfn_ar_log_prob / npfn_ar_fit_begin), whose
+// context table the call has just written into h->joint on s.  Without a fit token: fit0,
+// refitted every call.  With the token of the set in use (the accept/reject batches of one
+// sample() call, npe_pfn.py:284-292): that set, unchecked.  With a new token: the cached set
+// with an equal key whose table equals h->joint in every 32-bit pattern (one k_ctx_diff launch
+// over all candidates, one small copy back, one stream synchronize), else a free or the least
+// recently used set, whose slots are cleared and refitted.
+// `reuse`: the set's fitted slots are this call's fits (a slot not fitted yet is fitted in
+// order on s); otherwise every step is fitted (ar_prefit / ar_step_fit).
+int begin_ar_fits(npfn_engine* h, int64_t n, int dx, int dth, hipStream_t s, bool& reuse) {
+  reuse = false;
+  if (h->fit_token == 0) return NPFN_OK;
+  uint64_t key[kFitKey];
+  fit_key(h, n, dx, dth, key);
+  auto matches = [&](const FitSet& fs) {
+    return fs.valid && (int)fs.slots.size() >= dth && std::memcmp(key, fs.key, sizeof(key)) == 0;
+  };
+  if (h->cur && h->cur->token == h->fit_token && matches(*h->cur)) {
+    h->cur->stamp = ++h->lru_clock;
+    reuse = true;
+    return NPFN_OK;
+  }
+  const size_t n_ctx = (size_t)n * (dx + dth);
+  FitSet* hit = nullptr;
+  if (h->max_sets > 0) {
+    std::vector<FitSet*> cand;
+    for (auto& fs : h->sets)
+      if (matches(*fs)) cand.push_back(fs.get());
+    for (size_t c0 = 0; c0 < cand.size() && !hit; c0 += kCtxCopiesMax) {
+      const int nc = (int)std::min<size_t>(kCtxCopiesMax, cand.size() - c0);
+      if (!h->diff_dev) {
+        HIPCHK(hipMalloc((void**)&h->diff_dev, kCtxCopiesMax * sizeof(int32_t)));
+        HIPCHK(hipHostMalloc((void**)&h->diff_host, kCtxCopiesMax * sizeof(int32_t)));
+      }
+      CtxCopies cp{};
+      for (int c = 0; c < nc; ++c) {
+        // the copy was written on the stream of the call that filled the set
+        HIPCHK(hipStreamWaitEvent(s, cand[c0 + c]->ready, 0));
+        cp.p[c] = (const uint32_t*)cand[c0 + c]->ctx.p;
+      }
+      launch_ctx_diff((const float*)h->joint.p, cp, nc, (int64_t)n_ctx, h->diff_dev, s);
+      HIPCHK(hipMemcpyAsync(h->diff_host, h->diff_dev, nc * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));
+      for (int c = 0; c < nc && !hit; ++c)
+        if (h->diff_host[c] == 0) hit = cand[c0 + c];
+    }
+  }
+  FitSet* fs = hit;
+  if (!fs) {
+    for (auto& q : h->sets)  // a set that holds no fits
+      if (!q->valid && (!fs || q->stamp < fs->stamp)) fs = q.get();
+    if (!fs && (int)h->sets.size() < cache_capacity(h)) {
+      h->sets.emplace_back(new FitSet());
+      fs = h->sets.back().get();
+    }
+    if (!fs)  // evict the least recently used
+      for (auto& q : h->sets)
+        if (!fs || q->stamp < fs->stamp) fs = q.get();
+  }
+  RCHK(set_events(*fs));
+  // whatever still reads the set's slots or (a partly filled set, an eviction) will be
+  // overwritten: the earlier calls on their streams and the engine's side streams
+  for (hipEvent_t e : {fs->ready, fs->ready_side, fs->ready_train, fs->last_use}) HIPCHK(hipStreamWaitEvent(s, e, 0));
+  if (hit) {
+    ++h->cache_hits;
+    reuse = true;
+  } else {
+    ++h->cache_misses;
+    // until end_ar_fits.  A one-call entry point (npfn_ar_sample, ...) that fails therefore
+    // leaves no keyed set behind.  npfn_ar_fit_begin keys the set at its own end, with most
+    // slots still unfitted (`fitted` is set on the host when a slot's train forward has been
+    // queued, not when it has run): what holds there is only that a slot with fitted == false
+    // -- never queued, or its fit refused -- is fitted by whichever call needs it next
+    if ((int)fs->slots.size() < dth) {
+      if (set_owns(*fs, h->f)) h->f = &h->fit0;
+      fs->slots.resize(dth);
+    }
+    // a slot filled under another context, shape or estimator set is not a fit of this call
+    for (Fit& sl : fs->slots) sl.fitted = false;
+    if (h->max_sets > 0) {
+      RCHK(ensure(fs->ctx, n_ctx * sizeof(float), s));
+      HIPCHK(hipMemcpyAsync(fs->ctx.p, h->joint.p, n_ctx * sizeof(float), hipMemcpyDeviceToDevice, s));
+    }
+    std::memcpy(fs->key, key, sizeof(key));
+  }
+  fs->token = h->fit_token;
+  fs->stamp = ++h->lru_clock;
+  h->cur = fs;
+  return NPFN_OK;
+}
+// End of a call under a fit token, after its last read of the engine's shared workspaces (the
+// copies of h->feat / h->logp into the caller's outputs included): the set is keyed, its events
+// follow the call's work on s (and on the side streams when fits were piped), and the cache is
+// brought within its limits.
+int end_ar_fits(npfn_engine* h, bool piped, hipStream_t s) {
+  if (h->fit_token == 0) return NPFN_OK;
+  FitSet* fs = h->cur;
+  fs->valid = true;
+  HIPCHK(hipEventRecord(fs->ready, s));
+  HIPCHK(hipEventRecord(fs->last_use, s));
+  if (piped) {
+    HIPCHK(hipEventRecord(fs->ready_side, h->side));
+    HIPCHK(hipEventRecord(fs->ready_train, h->side_t));
+  }
+  h->last_stream = s;
+  h->last_stream_set = true;
+  const size_t b = set_bytes(*fs);
+  if (b != fs->bytes) {
+    fs->bytes = b;
+    cache_enforce(h, fs);
+  }
+  return NPFN_OK;
+}
+Fit* step_fit(npfn_engine* h, int k) { return h->fit_token != 0 ? &h->cur->slots[k] : &h->fit0; }
 
 // The fits of the AR steps (slot k: fit on x | theta[:, :k] -> theta[:, k]) depend on the
 // context only, not on the samples of the earlier steps, so with per-step slots they run
@@ -1187,9 +1425,10 @@ static const int kTrainAhead = [] {
 }();
 int ar_side_train(npfn_engine* h, const float* joint, int Ft, int64_t n, int F, int k) {
   hipStream_t t = h->side_t;
+  h->side_busy = true;
   Fit* keep_f = h->f;
   Work* keep_w = h->w;
-  h->f = &h->slots[k];
+  h->f = &h->cur->slots[k];
   h->w = &h->wside;
   int rc = hipStreamWaitEvent(t, h->stat_done[k], 0) == hipSuccess ? NPFN_OK : fail(NPFN_EHIP, "stream wait");
   if (rc == NPFN_OK) rc = fit_train(h, joint, Ft, joint + F, Ft, n, t);
@@ -1211,6 +1450,8 @@ int ar_prefit(npfn_engine* h, const float* joint, int Ft, int64_t n, int dx, int
     HIPCHK(hipStreamCreateWithPriority(&h->side, hipStreamNonBlocking, least));
     HIPCHK(hipStreamCreateWithPriority(&h->side_t, hipStreamNonBlocking, least));
     HIPCHK(hipEventCreateWithFlags(&h->setup_done, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&h->side_idle[0], hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&h->side_idle[1], hipEventDisableTiming));
   }
   while ((int)h->prep_done.size() < dth) {
     hipEvent_t e, e2;
@@ -1221,6 +1462,7 @@ int ar_prefit(npfn_engine* h, const float* joint, int Ft, int64_t n, int dx, int
   }
   // the context table was written on s, and the slots' buffers may still be read by s's work
   // of the previous call
+  h->side_busy = true;
   HIPCHK(hipEventRecord(h->setup_done, s));
   HIPCHK(hipStreamWaitEvent(h->side, h->setup_done, 0));
   HIPCHK(hipStreamWaitEvent(h->side_t, h->setup_done, 0));
@@ -1229,7 +1471,7 @@ int ar_prefit(npfn_engine* h, const float* joint, int Ft, int64_t n, int dx, int
   Fit* keep_f = h->f;
   for (int k = 0; k < dth; ++k) {
     const int F = dx + k;
-    h->f = &h->slots[k];
+    h->f = &h->cur->slots[k];
     int rc = fit_prep(h, joint, Ft, joint + F, Ft, n, F, h->side);
     if (rc == NPFN_OK && hipEventRecord(h->stat_done[k], h->side) != hipSuccess) rc = fail(NPFN_EHIP, "event");
     if (rc == NPFN_OK && k == 0) {  // step 0 on the main stream, in its own workspaces
@@ -1316,12 +1558,12 @@ int ar_sample_impl(npfn_engine* h, const float* x_ctx, const float* theta_ctx, i
     cellQ = pairQ + (size_t)n_unique * std::max(dim_theta - 1, 0) * GG;
     pbad = (int32_t*)(pairQ + pair_q);
   }
-  begin_ar_fits(h, n_ctx, dim_x, dim_theta, reuse);
+  RCHK(begin_ar_fits(h, n_ctx, dim_x, dim_theta, s, reuse));
   if (!reuse) RCHK(ar_prefit(h, joint, Ft, n_ctx, dim_x, dim_theta, s, piped));
   for (int k = 0; k < dim_theta; ++k) {
     const int F = dim_x + k;
     h->f = step_fit(h, k);
-    if (!reuse) RCHK(ar_step_fit(h, joint, Ft, n_ctx, dim_x, dim_theta, k, piped, s));
+    if (!reuse || !h->f->fitted) RCHK(ar_step_fit(h, joint, Ft, n_ctx, dim_x, dim_theta, k, piped, s));
     if (marg_out) launch_borders(h->bz, (const float*)h->f->ystats.p, nb, borders_out + (int64_t)k * (nb + 1), s);
     if (po && n_rows > 0) {  // this step's borders and zeroed tables
       launch_borders(h->bz, (const float*)h->f->ystats.p, nb, (float*)h->pairbd.p, s);
@@ -1393,10 +1635,10 @@ int ar_sample_impl(npfn_engine* h, const float* x_ctx, const float* theta_ctx, i
       launch_pair_final(cellQ, pbad, n_unique, G, per, po->cell_out + (int64_t)k * G, (int64_t)dim_theta * G, s);
     }
   }
-  end_ar_fits(h, n_ctx, dim_x, dim_theta);
   if (theta_out) launch_copy_cols(feat + dim_x, Ft, theta_out, dim_theta, n_rows, dim_theta, 0, s);
   if (log_prob_out && n_rows > 0)
     HIPCHK(hipMemcpyAsync(log_prob_out, h->logp.p, n_rows * sizeof(float), hipMemcpyDeviceToDevice, s));
+  RCHK(end_ar_fits(h, piped, s));
   HIPCHK(hipGetLastError());
   return NPFN_OK;
 }
@@ -1418,12 +1660,12 @@ int ar_log_prob_impl(npfn_engine* h, const float* x_ctx, const float* theta_ctx,
   float* feat = (float*)h->feat.p;
   launch_copy_cols(theta, dim_theta, feat, Ft, n_rows, dim_theta, dim_x, s);
   bool reuse = false, piped = false;
-  begin_ar_fits(h, n_ctx, dim_x, dim_theta, reuse);
+  RCHK(begin_ar_fits(h, n_ctx, dim_x, dim_theta, s, reuse));
   if (!reuse) RCHK(ar_prefit(h, joint, Ft, n_ctx, dim_x, dim_theta, s, piped));
   for (int k = 0; k < dim_theta; ++k) {
     const int F = dim_x + k;
     h->f = step_fit(h, k);
-    if (!reuse) RCHK(ar_step_fit(h, joint, Ft, n_ctx, dim_x, dim_theta, k, piped, s));
+    if (!reuse || !h->f->fitted) RCHK(ar_step_fit(h, joint, Ft, n_ctx, dim_x, dim_theta, k, piped, s));
     if (k == 0 && n_unique > 0 && n_rows > 0) {
       RCHK(ensure(h->pu, (size_t)n_unique * nb * sizeof(float), s));
       float* pu = (float*)h->pu.p;
@@ -1446,9 +1688,9 @@ int ar_log_prob_impl(npfn_engine* h, const float* x_ctx, const float* theta_ctx,
                      Ft, F, (float*)h->logp.p, log_eps, s);
     }
   }
-  end_ar_fits(h, n_ctx, dim_x, dim_theta);
   if (n_rows > 0)
     HIPCHK(hipMemcpyAsync(log_prob_out, h->logp.p, n_rows * sizeof(float), hipMemcpyDeviceToDevice, s));
+  RCHK(end_ar_fits(h, piped, s));
   HIPCHK(hipGetLastError());
   return NPFN_OK;
 }
@@ -1472,14 +1714,14 @@ int ar_score_impl(npfn_engine* h, const float* x_ctx, const float* theta_ctx, in
   float* feat = (float*)h->feat.p;
   launch_copy_cols(theta, dim_theta, feat, Ft, n_rows, dim_theta, dim_x, s);
   bool reuse = false, piped = false;
-  begin_ar_fits(h, n_ctx, dim_x, dim_theta, reuse);
+  RCHK(begin_ar_fits(h, n_ctx, dim_x, dim_theta, s, reuse));
   if (!reuse) RCHK(ar_prefit(h, joint, Ft, n_ctx, dim_x, dim_theta, s, piped));
   for (int k = 0; k < dim_theta; ++k) {
     const int F = dim_x + k;
     float* lpk = logp_steps ? logp_steps + k : nullptr;
     float* cdk = cdf_steps ? cdf_steps + k : nullptr;
     h->f = step_fit(h, k);
-    if (!reuse) RCHK(ar_step_fit(h, joint, Ft, n_ctx, dim_x, dim_theta, k, piped, s));
+    if (!reuse || !h->f->fitted) RCHK(ar_step_fit(h, joint, Ft, n_ctx, dim_x, dim_theta, k, piped, s));
     if (k == 0 && n_unique > 0 && n_rows > 0) {
       RCHK(ensure(h->pu, (size_t)n_unique * nb * sizeof(float), s));
       float* pu = (float*)h->pu.p;
@@ -1502,7 +1744,7 @@ int ar_score_impl(npfn_engine* h, const float* x_ctx, const float* theta_ctx, in
                        feat, Ft, F, lpk, cdk, dim_theta, log_eps, s);
     }
   }
-  end_ar_fits(h, n_ctx, dim_x, dim_theta);
+  RCHK(end_ar_fits(h, piped, s));
   HIPCHK(hipGetLastError());
   return NPFN_OK;
 }
@@ -1618,9 +1860,14 @@ int npfn_engine_destroy(npfn_engine* h) {
   for (hipEvent_t e : h->stat_done) (void)hipEventDestroy(e);
   if (h->side_t) (void)hipStreamDestroy(h->side_t);
   if (h->setup_done) (void)hipEventDestroy(h->setup_done);
+  for (hipEvent_t e : h->side_idle)
+    if (e) (void)hipEventDestroy(e);
   if (h->side) (void)hipStreamDestroy(h->side);
   h->fit0.release();
-  for (Fit& f : h->slots) f.release();
+  for (auto& fs : h->sets) set_destroy(h, *fs);
+  h->sets.clear();
+  if (h->diff_dev) (void)hipFree(h->diff_dev);
+  if (h->diff_host) (void)hipHostFree(h->diff_host);
   h->wmain.release();
   h->wside.release();
   DevBuf* bufs[] = {&h->dh,      &h->logits, &h->tgt,
@@ -1646,8 +1893,7 @@ int npfn_set_preprocessing(npfn_engine* h, int32_t mode) {
   RCHK(apply_preprocessing(h, mode));
   h->f = &h->fit0;
   h->f->fitted = false;
-  for (Fit& sl : h->slots) sl.fitted = false;
-  std::memset(h->slot_key, 0, sizeof(h->slot_key));
+  cache_invalidate(h);  // the pipelines' device tables were rewritten
   h->ar_active = false;
   return NPFN_OK;
 }
@@ -1949,15 +2195,16 @@ int npfn_ar_fit_begin(npfn_engine* h, const float* x_ctx, const float* theta_ctx
   const int Ft = dim_x + dim_theta;
   h->ar_active = false;
   RCHK(ensure_pipelines(h, false));
+  RCHK(order_after_last_call(h, s));
   RCHK(ensure(h->joint, (size_t)n_ctx * Ft * sizeof(float), s));
   float* joint = (float*)h->joint.p;
   launch_copy_cols(x_ctx, dim_x, joint, Ft, n_ctx, dim_x, 0, s);
   launch_copy_cols(theta_ctx, dim_theta, joint, Ft, n_ctx, dim_theta, dim_x, s);
   bool reuse = false, piped = false;
-  begin_ar_fits(h, n_ctx, dim_x, dim_theta, reuse);
+  RCHK(begin_ar_fits(h, n_ctx, dim_x, dim_theta, s, reuse));
   if (!reuse) RCHK(ar_prefit(h, joint, Ft, n_ctx, dim_x, dim_theta, s, piped));
   // the slots are keyed now; a slot's `fitted` says whether its train forward ran
-  end_ar_fits(h, n_ctx, dim_x, dim_theta);
+  RCHK(end_ar_fits(h, piped, s));
   h->ar_n = n_ctx;
   h->ar_dx = dim_x;
   h->ar_dth = dim_theta;
@@ -1973,12 +2220,15 @@ int npfn_ar_fit_step(npfn_engine* h, int32_t k, void* stream) {
   if (!h->ar_active) return fail(NPFN_ESTATE, "ar_fit_step before ar_fit_begin");
   if (k < 0 || k >= h->ar_dth) return fail(NPFN_EINVAL, "ar_fit_step: step out of range");
   const int Ft = h->ar_dx + h->ar_dth;
+  if (h->fit_token != 0 && (!h->cur || h->cur->token != h->fit_token))
+    return fail(NPFN_ESTATE, "ar_fit_step: the fit token changed since ar_fit_begin");
   h->f = step_fit(h, k);
-  // reuse: an earlier call under the same token, context shape and estimator set fitted every
-  // slot (nothing queued); a slot's `fitted` alone may be left over from another context
+  // reuse: the set was filled by an earlier call under this token or adopted from the fit
+  // cache (nothing queued); a step that call did not reach is fitted now, in order on `stream`
   if (h->ar_reuse && h->f->fitted) return NPFN_OK;
   RCHK(ar_step_fit(h, (const float*)h->joint.p, Ft, h->ar_n, h->ar_dx, h->ar_dth, k, h->ar_piped,
                    (hipStream_t)stream));
+  RCHK(end_ar_fits(h, h->ar_piped, (hipStream_t)stream));  // the set's events follow the new fit
   HIPCHK(hipGetLastError());
   return NPFN_OK;
 }
@@ -1987,6 +2237,38 @@ int npfn_set_fit_token(npfn_engine* h, uint64_t token) {
   RCHK(check_engine(h));
   h->fit_token = token;
   if (token == 0) h->f = &h->fit0;
+  return NPFN_OK;
+}
+
+int npfn_set_fit_cache(npfn_engine* h, int32_t max_sets, uint64_t max_bytes) {
+  RCHK(check_engine(h));
+  if (max_sets < 0) return fail(NPFN_EINVAL, "set_fit_cache: max_sets must be >= 0");
+  // sets filled while the cache was off hold no copy of their table to compare with
+  if (h->max_sets == 0 && max_sets > 0) cache_invalidate(h);
+  h->max_sets = max_sets;
+  h->max_bytes = (size_t)max_bytes;
+  cache_enforce(h, h->cur);
+  return NPFN_OK;
+}
+
+int npfn_fit_cache_stats(npfn_engine* h, uint64_t* hits, uint64_t* misses, int32_t* sets, uint64_t* bytes) {
+  RCHK(check_engine(h));
+  if (hits) *hits = h->cache_hits;
+  if (misses) *misses = h->cache_misses;
+  if (sets) {
+    *sets = 0;
+    for (auto& fs : h->sets) *sets += fs->valid ? 1 : 0;
+  }
+  if (bytes) *bytes = cache_bytes(h);
+  return NPFN_OK;
+}
+
+int npfn_fit_cache_clear(npfn_engine* h) {
+  RCHK(check_engine(h));
+  for (auto& fs : h->sets) set_destroy(h, *fs);
+  h->sets.clear();
+  h->cur = nullptr;
+  h->ar_active = false;
   return NPFN_OK;
 }
 
@@ -2004,8 +2286,8 @@ int npfn_set_estimator_set(npfn_engine* h, int32_t e0, int32_t count, int32_t st
   h->es = count == 1 ? 1 : stride;
   h->f = &h->fit0;
   h->f->fitted = false;
-  for (Fit& sl : h->slots) sl.fitted = false;  // per-estimator layouts of the old set
-  std::memset(h->slot_key, 0, sizeof(h->slot_key));
+  // the cached sets stay: the estimator set is part of their key (fit_key), so a set fitted
+  // under another estimator set is never adopted, and one fitted under this set is found again
   h->ar_active = false;
   return NPFN_OK;
 }

@@ -347,6 +347,14 @@ void launch_pair_final(const int64_t* Q, const int32_t* bad, int64_t n_unique, i
 void launch_copy_cols(const float* src, int64_t lds, float* dst, int64_t ldd, int64_t rows, int cols,
                       int dst_col0, hipStream_t s, int64_t per = 1);
 void launch_fill(float* dst, int64_t n, float v, hipStream_t s);
+// Fit cache (npfn_engine.hip begin_ar_fits): flags[c] = whether any of the n 32-bit patterns of
+// cur differs from cached context copy c, c < n_copies <= kCtxCopiesMax, all in one launch
+constexpr int kCtxCopiesMax = 16;
+struct CtxCopies {
+  const uint32_t* p[kCtxCopiesMax];
+};
+void launch_ctx_diff(const float* cur, const CtxCopies& copies, int n_copies, int64_t n, int32_t* flags,
+                     hipStream_t s);
 void launch_box_support(const float* th, int64_t n, int dim, const float* lo, const float* hi, uint8_t* mask,
                         hipStream_t s);
 // npfn_restricted.hip: one rejection round of the restricted prior.  Proposals out [n][dim] of

@@ -3474,6 +3474,19 @@ __global__ void k_fill(float* __restrict__ dst, int64_t n, float v) {
   if (i < n) dst[i] = v;
 }
 
+// Fit cache: flags[c] = 1 where the table `cur` differs from cached copy c in any 32-bit
+// pattern (NaN cells compare equal to themselves, +0 and -0 differ).  flags are zeroed by the
+// launcher; every differing thread stores the same 1, so no atomics are needed.
+__global__ void k_ctx_diff(const uint32_t* __restrict__ cur, CtxCopies copies, int64_t n,
+                           int32_t* __restrict__ flags) {
+  const int c = blockIdx.y;
+  const uint32_t* __restrict__ old = copies.p[c];
+  bool diff = false;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    diff |= cur[i] != old[i];
+  if (diff) flags[c] = 1;
+}
+
 __global__ void k_box_support(const float* __restrict__ th, int64_t n, int dim, const float* __restrict__ lo,
                               const float* __restrict__ hi, uint8_t* __restrict__ mask) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -3951,6 +3964,15 @@ void launch_copy_cols(const float* src, int64_t lds, float* dst, int64_t ldd, in
 void launch_fill(float* dst, int64_t n, float v, hipStream_t s) {
   if (n == 0) return;
   hipLaunchKernelGGL(k_fill, dim3(blocks_for(n, 256)), dim3(256), 0, s, dst, n, v);
+}
+void launch_ctx_diff(const float* cur, const CtxCopies& copies, int n_copies, int64_t n, int32_t* flags,
+                     hipStream_t s) {
+  if (n_copies <= 0) return;
+  (void)hipMemsetAsync(flags, 0, (size_t)n_copies * sizeof(int32_t), s);
+  if (n == 0) return;
+  const unsigned bx = (unsigned)std::min<int64_t>(blocks_for(n, 256), 1024);
+  hipLaunchKernelGGL(k_ctx_diff, dim3(bx, (unsigned)n_copies), dim3(256), 0, s, (const uint32_t*)cur, copies, n,
+                     flags);
 }
 void launch_box_support(const float* th, int64_t n, int dim, const float* lo, const float* hi, uint8_t* mask,
                         hipStream_t s) {

@@ -121,6 +121,10 @@ SIGNATURES = {
     "npfn_ar_fit_begin": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp]),
     "npfn_ar_fit_step": (ctypes.c_int, [_vp, _i32, _vp]),
     "npfn_set_fit_token": (ctypes.c_int, [_vp, _u64]),
+    "npfn_set_fit_cache": (ctypes.c_int, [_vp, _i32, _u64]),
+    "npfn_fit_cache_stats": (ctypes.c_int, [_vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_i32),
+                                            ctypes.POINTER(_u64)]),
+    "npfn_fit_cache_clear": (ctypes.c_int, [_vp]),
     "npfn_set_chunk_rows": (ctypes.c_int, [_vp, _i64]),
     "npfn_prof_enable": (ctypes.c_int, [_vp, ctypes.c_int]),
     "npfn_prof_read": (ctypes.c_int, [_vp, ctypes.POINTER(NpfnProfEntry), _i32, ctypes.POINTER(_i32)]),
@@ -920,6 +924,26 @@ class Engine:
         """npfn_set_fit_token: ar_sample / ar_log_prob calls under one non-zero token reuse the
         per-step fits of the first (the context must be the same for all of them)."""
         _check(self.lib, self.lib.npfn_set_fit_token(self.h, int(token) & 0xFFFFFFFFFFFFFFFF), "npfn_set_fit_token")
+
+    def set_fit_cache(self, max_sets: int = 1, max_bytes: int = 0) -> None:
+        """npfn_set_fit_cache: how many sets of per-step fits the engine keeps across fit tokens
+        (a call under a new token whose context table equals a cached set's, bit for bit, refits
+        nothing; 0 = no reuse across tokens) and the device memory they may hold (0 = no limit)."""
+        _check(self.lib, self.lib.npfn_set_fit_cache(self.h, int(max_sets), int(max_bytes)), "npfn_set_fit_cache")
+
+    def fit_cache_stats(self) -> dict:
+        """npfn_fit_cache_stats: {hits, misses, sets, bytes} of the fit cache."""
+        hits, misses, nbytes = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        sets = ctypes.c_int32(0)
+        _check(self.lib, self.lib.npfn_fit_cache_stats(self.h, ctypes.byref(hits), ctypes.byref(misses),
+                                                       ctypes.byref(sets), ctypes.byref(nbytes)),
+               "npfn_fit_cache_stats")
+        return {"hits": int(hits.value), "misses": int(misses.value), "sets": int(sets.value),
+                "bytes": int(nbytes.value)}
+
+    def fit_cache_clear(self) -> None:
+        """npfn_fit_cache_clear: free every cached set of fits."""
+        _check(self.lib, self.lib.npfn_fit_cache_clear(self.h), "npfn_fit_cache_clear")
 
     def set_chunk_rows(self, rows: int) -> None:
         """Query rows per forward chunk (npfn_set_chunk_rows; default 16384)."""

@@ -1018,21 +1018,45 @@ class TabPFN_Based_Uncond_Estimator(NPE_PFN_Core):
         counts = self.kmeans.counts.numpy()
         assert counts.min() > 1, "Too few samples in some clusters, need at least 2."
         self.counts = counts
+        self._size_fit_cache()
         return self
+
+    # share of the device's free memory the clusters' cached fits may hold
+    FIT_CACHE_FREE_FRACTION = 0.5
+
+    def _size_fit_cache(self):
+        """One cached set of per-step fits per cluster (TabPFNRegressor.size_fit_cache): from the
+        second ``sample`` / ``log_prob`` on no cluster is refitted.  The sets may hold at most
+        ``FIT_CACHE_FREE_FRACTION`` of the memory that is free on the device when the limit is
+        applied (after clustering; after unpickling, when the engine is rebuilt) -- the rest stays
+        for the forwards' workspaces and the caller; past the limit the engine frees the least
+        recently used clusters' fits and refits them when they come round again.
+        ``regressor_init_kwargs["fit_cache_sets"] = 0`` is honoured: the cache stays off and every
+        call refits, as the reference does."""
+        if not self._fused() or self._model.fit_cache_sets == 0:
+            return
+        self._model.size_fit_cache(max(int(self.num_clusters), 1), self.FIT_CACHE_FREE_FRACTION)
+
+    def __setstate__(self, state):
+        super().__setstate__(state)   # a new regressor without an engine
+        if self.kmeans is not None:
+            self._size_fit_cache()    # recorded on the regressor, applied when its engine is built
 
     def sample(self, sample_shape: torch.Size = torch.Size(), x: Tensor = None, max_sampling_batch_size: int = 10_000,
                with_log_prob: bool = False, eps: float = 1e-15) -> Union[Tensor, Tuple[Tensor, Tensor]]:
         """``sample_shape[0]`` draws of the mixture (reference :802-844); ``x`` is ignored.
 
-        No fit token: the engine keeps one set of cached fits, and every cluster has its own context."""
+        Every cluster visit runs under its own fit token; the engine's fit cache holds one set of
+        fits per cluster (:meth:`_size_fit_cache`), found again by the cluster's context."""
         per_cluster = np.random.multinomial(sample_shape[0], self.counts / self.counts.sum())
         draws, lps = [], []
         for c, m in enumerate(per_cluster):
             self.set_cluster_state(c)
             if m == 0:
                 continue
-            th, lp = self._sample(max_sampling_batch_size, torch.randn(int(m), 1), repeat_x=False,
-                                  with_log_prob=with_log_prob, eps=eps)
+            with self._reuse_fits():
+                th, lp = self._sample(max_sampling_batch_size, torch.randn(int(m), 1), repeat_x=False,
+                                      with_log_prob=with_log_prob, eps=eps)
             draws.append(th)
             lps.append(lp)
         self.set_cluster_state()
@@ -1102,7 +1126,8 @@ class TabPFN_Based_Uncond_Estimator(NPE_PFN_Core):
         """log of the mixture's component density at theta's own cluster plus the log cluster
         weight (reference :846-900); ``x`` is ignored.  Every cluster visit takes a fresh fit
         token around its chunks: a token kept across clusters would let two clusters of equal
-        size reuse each other's fits."""
+        size reuse each other's fits.  Under a fresh token the engine's fit cache finds the
+        cluster's fits by the content of its context (:meth:`_size_fit_cache`)."""
         if mode == "ratio_based":
             raise NotImplementedError(
                 "TabPFN_Based_Uncond_Estimator.log_prob: mode='ratio_based' is not provided (the reference's "

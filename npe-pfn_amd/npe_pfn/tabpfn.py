@@ -146,7 +146,8 @@ class TabPFNRegressor:
 
     def __init__(self, n_estimators: int = 8, softmax_temperature: float = 0.9, random_state: Optional[int] = 0,
                  device="auto", model_path="auto", weights=None, weight_seed: int = 0,
-                 preprocessing: str = "ensemble", ignore_pretraining_limits: bool = False, **kwargs):
+                 preprocessing: str = "ensemble", ignore_pretraining_limits: bool = False, fit_cache_sets: int = 1,
+                 **kwargs):
         kw = _take_kwargs("TabPFNRegressor", kwargs, classifier=False)
         self.average_before_softmax = kw["average_before_softmax"]
         self.inference_precision = kw["inference_precision"]
@@ -161,6 +162,13 @@ class TabPFNRegressor:
         # "ensemble" (tabpfn's default regressor preprocessing) | "none" | "quantile" |
         # "quantile+power" (Engine.set_preprocessing)
         self.preprocessing = preprocessing
+        # sets of per-step fits the engine keeps across sample() / log_prob() calls
+        # (Engine.set_fit_cache): a call whose context equals a cached one refits nothing.
+        # 1 = the memory one call holds anyway; 0 = refit on every call, as the reference does
+        self.fit_cache_sets = int(fit_cache_sets)
+        # byte limit of the cached sets as a share of the device memory that is free when the limit
+        # is applied (None: no limit); set through :meth:`size_fit_cache`
+        self.fit_cache_free_fraction = None
         self.sample_counter = 0
         self._engine = None
 
@@ -181,7 +189,27 @@ class TabPFNRegressor:
                                   preprocessing=self.preprocessing)
             if self.average_before_softmax:
                 self._engine.set_average_before_softmax(True)
+            if getattr(self, "fit_cache_sets", 1) != 1 or getattr(self, "fit_cache_free_fraction", None):
+                self._apply_fit_cache(self._engine)
         return self._engine
+
+    def _apply_fit_cache(self, eng) -> None:
+        frac = getattr(self, "fit_cache_free_fraction", None)
+        max_bytes = 0
+        if frac:
+            with torch.cuda.device(eng.device):
+                free, _total = torch.cuda.mem_get_info()
+            max_bytes = max(int(free * float(frac)), 1)
+        eng.set_fit_cache(getattr(self, "fit_cache_sets", 1), max_bytes)
+
+    def size_fit_cache(self, sets: int, free_fraction: Optional[float] = None) -> None:
+        """Keep ``sets`` sets of per-step fits across calls, holding at most ``free_fraction`` of the
+        device memory that is free when the limit is applied (None: no limit).  Applied at once when
+        the engine exists, else when it is created -- also after unpickling, which drops the engine."""
+        self.fit_cache_sets = int(sets)
+        self.fit_cache_free_fraction = free_fraction
+        if self._engine is not None:
+            self._apply_fit_cache(self._engine)
 
     def __getstate__(self):
         st = self.__dict__.copy()
@@ -313,7 +341,9 @@ class TabPFNRegressor:
     @contextlib.contextmanager
     def reuse_fits(self):
         """Within the block, ar_sample / ar_log_prob calls share their per-step fits (one fresh
-        token; the caller guarantees one context for the whole block -- one sample() call)."""
+        token; the caller guarantees one context for the whole block -- one sample() call).
+        Across blocks the engine's fit cache decides: the first call under the fresh token
+        compares its context with the cached one and refits only when it differs."""
         eng = self.engine
         eng.set_fit_token(next(_FIT_TOKENS))
         try:
