@@ -481,6 +481,47 @@ int npfn_pair_accumulate(const double* w, const float* theta, int64_t ldt, int32
                          int32_t n_cells, int64_t r0, int64_t n_rows, int64_t per, int64_t* pairQ,
                          int64_t* cellQ, int32_t* bad, void* stream);
 
+/* MMD two-sample sums (npe_pfn.diagnostics.mmd_batched; the reference's MMD, scripts/
+ * evaluate_ropefm.py:283-320, with a permutation null; needs no engine).  z [n_obs, N = n_pool,
+ * dim] (device): observation u's pooled sample, both sets stacked.  bandwidths [n_bw] is a HOST
+ * array of the a_b (the one host pointer among this header's device pointers; read before the
+ * call returns).  labels [n_label, N] uint8 (device), shared by all observations: row p marks
+ * (non-zero) the points of group X under labelling p -- row 0 the observed split, the others
+ * permutations of it.  Outputs (device), ZEROED BY THE CALL itself on `stream`: sums [n_obs,
+ * n_label, 2] int64, total [n_obs] int64, bad [n_obs] int32.
+ *  - d2(i, j), fp32: acc = 0; for k ascending t = fl(z_i[k] - z_j[k]), acc = fl(acc + fl(t * t)),
+ *    every operation rounded on its own (no fused multiply-add, as in npfn_box_propose), so d2 is
+ *    bitwise symmetric and d2(i, i) = 0;
+ *  - kernel = 0 (rbf, the reference's exp(-0.5 d2 / a)): c_b = fl(-0.5f / a_b) on the host, k_b =
+ *    expf(fl(d2 * c_b)) with the accurate expf;
+ *  - kernel = 1 (multiscale, the reference's a^2 / (a^2 + d2)): s_b = fl(a_b * a_b) on the host,
+ *    k_b = fl(s_b / fl(s_b + d2)), the division correctly rounded;
+ *  - q(i, j) = sum over b of llrint((double)k_b * 2^28) (round half to even); k_b <= 1 and n_bw <=
+ *    8, so q <= 2^31 and q(i, i) = n_bw * 2^28 exactly;
+ *  - over ORDERED pairs, the diagonal included: sums[u][p][0] = sum of q(i, j) over the i, j with
+ *    labels[p][i] and labels[p][j] both set, sums[u][p][1] the same with both clear, total[u] the
+ *    sum over all N^2 pairs (the cross sum of a labelling is total - sums[0] - sums[1]).
+ * Fixed point makes the sums integers: they do not depend on the order of arrival, so the result
+ * is bitwise reproducible whatever the launch geometry or the other observations of the call, and
+ * multiscale equals the torch restatement npe_pfn.diagnostics.mmd_sums_host exactly (rbf to
+ * expf's last bit: 2^-23 of k_b, 32 units, per pair and bandwidth).  An observation with a
+ * non-finite coordinate gets bad[u] = 1; its sums are then unspecified.
+ * Kernel: one workgroup per (tile I of 64 points, strip of 8 tiles J >= I, observation, slab of 256
+ * labellings).  Both tiles' coordinates are staged in LDS, every q of the tile pair is computed
+ * once into an LDS tile cut into byte planes, and thread t folds it into labelling slab * 256 + t:
+ * its labels are two 64-bit masks built with a ballot, the bytes of q are read by LDS broadcast
+ * and summed per plane with v_dot4_u32_u8 (exact in 32 bits), the planes recombined in int64.  An
+ * off-diagonal tile pair counts twice.  One 64-bit integer add per workgroup and non-zero
+ * counter.  Neither an N x N nor an N x n_label array reaches global memory.  Asynchronous;
+ * n_obs == 0 launches nothing.
+ * Errors (host, before any launch): NPFN_EINVAL (message starting "mmd_sums") for n_obs < 0,
+ * n_pool outside 1..32768 (N^2 * 2^31 <= 2^61 keeps the int64 sums exact), dim outside 1..64,
+ * kernel not 0 or 1, n_bw outside 1..8, a bandwidth that is not finite and > 0, n_label outside
+ * 1..4096, or a missing pointer. */
+int npfn_mmd_sums(const float* z, int64_t n_obs, int64_t n_pool, int32_t dim, int32_t kernel,
+                  const float* bandwidths, int32_t n_bw, const uint8_t* labels, int32_t n_label,
+                  int64_t* sums, int64_t* total, int32_t* bad, void* stream);
+
 /* K12 standardized-Euclidean context filter (support_posterior.py:357-369):
  * idx_out[0:k] = indices of the k rows of x [n_rows, dim] closest to obs in
  * z-scored Euclidean distance, ascending (ties by lower index). */

@@ -7,7 +7,8 @@ this directory (``npe-pfn_amd``) on ``sys.path``.  The TabPFN forward runs in
 the HIP engine ``npe_pfn/_lib/libnpfn.so`` (C-ABI: include/npfn.h).
 """
 
-from npe_pfn.diagnostics import (CoverageRanks, bar_cdf, expected_coverage, pit_ks_statistic, rank_accumulate_host,
+from npe_pfn.diagnostics import (CoverageRanks, TwoSampleResult, bar_cdf, expected_coverage, mmd_batched,
+                                 mmd_sums_host, permutation_labels, pit_ks_statistic, rank_accumulate_host,
                                  rank_ks_statistic)
 from npe_pfn.marginals import PosteriorMarginals
 from npe_pfn.npe_pfn import NPE_PFN_Core, TabPFN_Based_NPE_PFN, TabPFN_Based_Uncond_Estimator
@@ -23,8 +24,12 @@ __all__ = [
     "PosteriorPairMarginals",
     "TabPFN_Based_NPE_PFN",
     "TabPFN_Based_Uncond_Estimator",
+    "TwoSampleResult",
     "bar_cdf",
     "expected_coverage",
+    "mmd_batched",
+    "mmd_sums_host",
+    "permutation_labels",
     "pit_ks_statistic",
     "rank_accumulate_host",
     "rank_ks_statistic",

@@ -12,6 +12,10 @@ definition of the engine's ``npfn_rank_accumulate`` (and the path of estimators 
 ``CoverageRanks`` holds the simulation-based-calibration, HPD and TARP ranks it yields, and
 ``rank_ks_statistic`` / ``expected_coverage`` turn ranks into a uniformity distance and a coverage
 curve.
+
+Distance between two sets of draws (``mmd_batched``, ``NPE_PFN_Core.mmd_batched``): the reference
+harness's MMD with a permutation null.  ``mmd_sums_host`` is the definition of the engine's
+``npfn_mmd_sums``, ``permutation_labels`` the relabellings, ``TwoSampleResult`` what comes back.
 """
 
 from __future__ import annotations
@@ -22,6 +26,8 @@ from typing import Optional, Tuple
 
 import torch
 from torch import Tensor
+
+from .engine import MMD_MAX_LABELLINGS, check_mmd_args
 
 HALFNORMAL_MEDIAN = 0.6744897501960817  # median of |N(0, 1)|: the tail bars' scale is width / this
 
@@ -249,3 +255,168 @@ def expected_coverage(ranks, num_samples: int, levels=None) -> Tuple[Tensor, Ten
     frac = r.to(torch.float64) / S
     ecp = (frac[None] < lv.reshape(-1, *([1] * r.ndim))).to(torch.float64).mean(1)
     return lv, ecp
+
+
+# ------------------------------------------------------------------ MMD two-sample test
+MMD_SCALE = float(2 ** 28)   # npfn_mmd_sums' fixed point: q = sum_b round(k_b * 2^28)
+MMD_DEFAULT_BANDWIDTHS = {"rbf": (10.0, 15.0, 20.0, 50.0), "multiscale": (0.2, 0.5, 0.9, 1.3)}
+
+
+def mmd_sums_host(z, labels, kernel, bandwidths) -> Tuple[Tensor, Tensor, Tensor]:
+    """``(sums [n_obs, n_label, 2] int64, total [n_obs] int64, bad [n_obs] int32)`` -- the
+    definition of the engine's ``npfn_mmd_sums`` (``Engine.mmd_sums``, same arguments), in torch on
+    the CPU.
+
+    ``z`` [n_obs, N, dim] is every observation's pooled sample (both sets stacked), ``labels``
+    [n_label, N] marks (non-zero) the points of group X under each labelling, ``kernel`` is "rbf" /
+    "multiscale" (0 / 1), ``bandwidths`` the a_b (1..8 of them).  In fp32, every operation rounded
+    on its own: d2(i, j) = sum over k ascending of t * t, t = z_i[k] - z_j[k]; k_b = exp(d2 * c_b),
+    c_b = -0.5 / a_b (rbf) or s_b / (s_b + d2), s_b = a_b * a_b (multiscale).  q(i, j) = sum over b
+    of round(k_b * 2^28) (fp64 product, round half to even), an integer.  Over ORDERED pairs, the
+    diagonal included: sums[u, p, 0] adds q over the pairs inside group X of labelling p, sums[u,
+    p, 1] over the pairs inside its complement, total[u] over all N^2 pairs.  An observation with a
+    non-finite coordinate gets bad[u] = 1 and zero sums (the engine leaves them unspecified).
+    Multiscale equals the engine exactly; rbf to the last bit of the two exp."""
+    z = torch.as_tensor(z).detach().to(device="cpu", dtype=torch.float32)
+    labels = torch.as_tensor(labels).detach().cpu()
+    code, bw = check_mmd_args(z.shape, labels.shape, kernel, bandwidths)
+    n_obs, N, dim = z.shape
+    L = (labels != 0).to(torch.int64)
+    Lc = 1 - L
+    a = torch.tensor(bw, dtype=torch.float32)
+    c = torch.tensor(-0.5, dtype=torch.float32) / a if code == 0 else a * a
+    sums = torch.zeros((n_obs, L.shape[0], 2), dtype=torch.int64)
+    total = torch.zeros(n_obs, dtype=torch.int64)
+    bad = torch.zeros(n_obs, dtype=torch.int32)
+    for u in range(n_obs):
+        zu = z[u]
+        if not bool(torch.isfinite(zu).all()):
+            bad[u] = 1
+            continue
+        d2 = torch.zeros((N, N), dtype=torch.float32)
+        for k in range(dim):   # ascending, one rounding per operation: the kernel's own chain
+            t = zu[:, None, k] - zu[None, :, k]
+            d2 = d2 + t * t
+        q = torch.zeros((N, N), dtype=torch.int64)
+        for b in range(len(bw)):
+            kb = torch.exp(d2 * c[b]) if code == 0 else c[b] / (c[b] + d2)
+            q += torch.round(kb.to(torch.float64) * MMD_SCALE).to(torch.int64)
+        sums[u, :, 0] = ((L @ q) * L).sum(1)
+        sums[u, :, 1] = ((Lc @ q) * Lc).sum(1)
+        total[u] = q.sum()
+    return sums, total, bad
+
+
+def permutation_labels(n: int, m: int, num_permutations: int, seed: int = 0) -> Tensor:
+    """Group labels of a permutation test on n + m pooled points: uint8 [num_permutations + 1, n +
+    m] (CPU).  Row 0 is n ones followed by m zeros (the observed split); row p >= 1 marks the
+    first n entries of the p-th ``torch.randperm(n + m)`` of a CPU ``torch.Generator`` seeded with
+    ``seed``, so a seed gives the same labels on every machine.  Every row has exactly n ones."""
+    n, m, P = int(n), int(m), int(num_permutations)
+    if n < 1 or m < 1 or P < 0:
+        raise ValueError(f"permutation_labels: need n >= 1, m >= 1 and num_permutations >= 0, got {n}, {m}, {P}")
+    gen = torch.Generator().manual_seed(int(seed))
+    lab = torch.zeros((P + 1, n + m), dtype=torch.uint8)
+    lab[0, :n] = 1
+    for p in range(1, P + 1):
+        lab[p, torch.randperm(n + m, generator=gen)[:n]] = 1
+    return lab
+
+
+@dataclass
+class TwoSampleResult:
+    """Maximum mean discrepancy between two sets of draws per observation (:func:`mmd_batched`),
+    float64 on the device of the draws.  ``mmd2_biased`` [M] is the reference's statistic
+    mean(k(x, x')) + mean(k(y, y')) - 2 mean(k(x, y)), the kernels summed over ``bandwidths`` and
+    the diagonals included; ``mmd2_unbiased`` [M] drops the diagonals (NaN for n < 2 or m < 2).
+    ``null`` [M, P] is the biased statistic under each of P random relabellings of the pooled
+    points and ``p_value`` [M] = (1 + #{null >= observed}) / (P + 1) (None for P = 0).  An
+    observation with a non-finite draw is NaN everywhere.  ``n`` / ``m`` are the sizes of the two
+    sets."""
+
+    mmd2_biased: Tensor
+    mmd2_unbiased: Tensor
+    null: Tensor
+    p_value: Optional[Tensor]
+    n: int
+    m: int
+    kernel: str
+    bandwidths: Tuple[float, ...]
+
+
+def mmd_p_value(observed: Tensor, null: Tensor) -> Tensor:
+    """(1 + #{p : null[..., p] >= observed[...]}) / (P + 1): the permutation p-value, in {1 / (P +
+    1), ..., 1}; NaN where ``observed`` is NaN."""
+    P = null.shape[-1]
+    p = (1 + (null >= observed[..., None]).sum(-1)).to(torch.float64) / (P + 1)
+    return torch.where(torch.isnan(observed), torch.full_like(p, float("nan")), p)
+
+
+def mmd_batched(a, b, kernel: str = "rbf", bandwidths=None, num_permutations: int = 0, seed: int = 0,
+                z_score: bool = False, engine=None) -> TwoSampleResult:
+    """MMD two-sample test between ``a`` [M, n, d] and ``b`` [M, m, d], observation by observation
+    (2-D inputs: M = 1), with a permutation null: the reference's MMD (scripts/
+    evaluate_ropefm.py:283-320) for n != m too, and a p-value to read it by.
+
+    ``kernel`` "rbf" sums exp(-0.5 d2 / a) and "multiscale" a^2 / (a^2 + d2) over ``bandwidths``
+    (default: the reference's, [10, 15, 20, 50] / [0.2, 0.5, 0.9, 1.3]; at most 8).
+    ``num_permutations`` P <= 4095 relabellings (:func:`permutation_labels` with ``seed``, shared by
+    all observations) give ``null`` and ``p_value``.  ``z_score=True`` standardises both sets by
+    ``a``'s per-observation mean and unbiased std first (a zero std counts as 1), as the
+    reference's C2ST does.  n + m <= 32768, d <= 64.
+
+    Tensors on the GPU go through ``npfn_mmd_sums`` (``engine.mmd_sums`` when an engine is given,
+    otherwise the library's engine-free entry): every kernel value is computed once, quantised
+    to 2^-28 and folded into all P + 1 labellings on the device; no n x n matrix is stored.  CPU
+    tensors go through :func:`mmd_sums_host`, the same statement in torch.  The statistics are
+    formed in fp64 from the integer sums."""
+    a, b = torch.as_tensor(a).detach(), torch.as_tensor(b).detach()
+    if kernel not in MMD_DEFAULT_BANDWIDTHS:
+        raise ValueError(f"mmd_batched: kernel must be 'rbf' or 'multiscale', got {kernel!r}")
+    if a.ndim == 2 and b.ndim == 2:
+        a, b = a[None], b[None]
+    if a.ndim != 3 or b.ndim != 3 or a.shape[0] != b.shape[0] or a.shape[2] != b.shape[2] or a.shape[1] < 1 \
+            or b.shape[1] < 1:
+        raise ValueError(f"mmd_batched: a {tuple(a.shape)} and b {tuple(b.shape)} are not [M, n >= 1, d] and "
+                         "[M, m >= 1, d] (or [n, d] and [m, d])")
+    P = int(num_permutations)
+    if not 0 <= P <= MMD_MAX_LABELLINGS - 1:
+        raise ValueError(f"mmd_batched: num_permutations must lie in 0..{MMD_MAX_LABELLINGS - 1}, got {P}")
+    n, m = a.shape[1], b.shape[1]
+    if z_score and n < 2:
+        raise ValueError("mmd_batched: z_score needs n >= 2 draws in a (the unbiased std)")
+    bw = MMD_DEFAULT_BANDWIDTHS[kernel] if bandwidths is None else bandwidths
+    dev = a.device
+    a, b = a.to(torch.float32), b.to(device=dev, dtype=torch.float32)
+    z = torch.cat([a, b], 1)
+    _, bw = check_mmd_args(z.shape, (P + 1, n + m), kernel, bw)
+    if z_score:
+        mu, sd = a.mean(1, keepdim=True), a.std(1, keepdim=True)
+        z = (z - mu) / torch.where(sd == 0, torch.ones_like(sd), sd)
+    labels = permutation_labels(n, m, P, seed)
+    if dev.type == "cuda":
+        from .engine import mmd_sums
+
+        sums, total, bad = engine.mmd_sums(z, labels, kernel, bw) if engine is not None else \
+            mmd_sums(z, labels, kernel, bw)
+    else:
+        sums, total, bad = mmd_sums_host(z, labels, kernel, bw)
+    sums, total, bad = sums.to(dev), total.to(dev), bad.to(dev)
+
+    B = len(bw)
+    diag = B * 2 ** 28   # q(i, i) exactly
+    f64 = lambda t: t.to(torch.float64)  # noqa: E731
+    XX, YY = f64(sums[:, :, 0]) / MMD_SCALE, f64(sums[:, :, 1]) / MMD_SCALE
+    XY = f64(total[:, None] - sums[:, :, 0] - sums[:, :, 1]) / (2 * MMD_SCALE)
+    stat = XX / (n * n) + YY / (m * m) - 2 * XY / (n * m)
+    if n >= 2 and m >= 2:
+        unbiased = (f64(sums[:, 0, 0] - n * diag) / MMD_SCALE / (n * (n - 1))
+                    + f64(sums[:, 0, 1] - m * diag) / MMD_SCALE / (m * (m - 1)) - 2 * XY[:, 0] / (n * m))
+    else:
+        unbiased = torch.full_like(stat[:, 0], float("nan"))
+    nan = bad != 0
+    stat = torch.where(nan[:, None], torch.full_like(stat, float("nan")), stat)
+    unbiased = torch.where(nan, torch.full_like(unbiased, float("nan")), unbiased)
+    biased, null = stat[:, 0].contiguous(), stat[:, 1:].contiguous()
+    return TwoSampleResult(biased, unbiased, null, mmd_p_value(biased, null) if P > 0 else None, n, m, kernel,
+                           tuple(bw))

@@ -12,6 +12,7 @@ valid inside the engine.
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 from typing import Dict, Optional, Tuple
 
@@ -109,6 +110,8 @@ SIGNATURES = {
     "npfn_bar_cell_mass": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp]),
     "npfn_pair_accumulate": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _i32, _i64, _i64, _i64, _vp, _vp,
                                             ctypes.POINTER(_i32), _vp]),
+    "npfn_mmd_sums": (ctypes.c_int, [_vp, _i64, _i64, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp,
+                                     ctypes.POINTER(_i32), _vp]),
     "npfn_filter_stdeuclid": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i64, _vp, _vp]),
     "npfn_sir_select": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _u64, _u64, _i64, _vp, _i32, _vp, _vp, _vp, _vp]),
     "npfn_kmeans_fit": (ctypes.c_int, [_vp, _i64, _i32, _i32, _u64, _i32, _f, _vp, _vp, _vp, _vp, _vp]),
@@ -185,6 +188,61 @@ def _check(lib, rc: int, what: str):
 def _dev_f32(t, device) -> torch.Tensor:
     t = torch.as_tensor(t)
     return t.to(device=device, dtype=torch.float32).contiguous()
+
+
+MMD_KERNELS = {"rbf": 0, "multiscale": 1}   # npfn_mmd_sums' kernel codes
+MMD_MAX_POOL, MMD_MAX_DIM, MMD_MAX_BANDWIDTHS, MMD_MAX_LABELLINGS = 32768, 64, 8, 4096
+
+
+def check_mmd_args(z_shape, labels_shape, kernel, bandwidths) -> Tuple[int, list]:
+    """(kernel code, bandwidths as floats) of an mmd_sums call on ``z`` [n_obs, N, dim] and
+    ``labels`` [n_label, N]; ValueError for whatever npfn_mmd_sums would refuse.  Pure host logic,
+    shared by :func:`mmd_sums` and :func:`npe_pfn.diagnostics.mmd_sums_host`."""
+    if kernel not in MMD_KERNELS and kernel not in (0, 1):
+        raise ValueError(f"mmd_sums: kernel must be 'rbf' (0) or 'multiscale' (1), got {kernel!r}")
+    code = MMD_KERNELS.get(kernel, kernel)
+    if len(z_shape) != 3 or not 1 <= z_shape[1] <= MMD_MAX_POOL or not 1 <= z_shape[2] <= MMD_MAX_DIM:
+        raise ValueError(f"mmd_sums: z {tuple(z_shape)} is not [n_obs, 1 <= N <= {MMD_MAX_POOL}, 1 <= dim <= "
+                         f"{MMD_MAX_DIM}]")
+    if len(labels_shape) != 2 or labels_shape[1] != z_shape[1] or not 1 <= labels_shape[0] <= MMD_MAX_LABELLINGS:
+        raise ValueError(f"mmd_sums: labels {tuple(labels_shape)} is not [1 <= n_label <= {MMD_MAX_LABELLINGS}, "
+                         f"{z_shape[1]}]")
+    bw = [float(a) for a in np.asarray(bandwidths, dtype=np.float64).reshape(-1)]
+    if not 1 <= len(bw) <= MMD_MAX_BANDWIDTHS or not all(math.isfinite(a) and a > 0 for a in bw):
+        raise ValueError(f"mmd_sums: need 1..{MMD_MAX_BANDWIDTHS} finite bandwidths > 0, got {bw}")
+    return int(code), bw
+
+
+def mmd_sums(z, labels, kernel, bandwidths, lib=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """npfn_mmd_sums on the GPU that holds ``z`` (needs no engine): ``(sums [n_obs, n_label, 2]
+    int64, total [n_obs] int64, bad [n_obs] int32)`` on that device, on its current stream.  ``z``
+    [n_obs, N, dim] is every observation's pooled sample, ``labels`` [n_label, N] (bool / uint8)
+    marks group X per labelling, ``kernel`` is "rbf" / "multiscale" (or 0 / 1), ``bandwidths`` the
+    a_b.  sums[u, p, 0] / [u, p, 1] are the fixed-point kernel sums over the ordered pairs inside
+    group X / inside its complement, total[u] the sum over all pairs; the definition of every
+    number: :func:`npe_pfn.diagnostics.mmd_sums_host`.  ValueError for arguments that do not fit,
+    before the C call."""
+    z = torch.as_tensor(z)
+    if z.device.type != "cuda":
+        raise ValueError("mmd_sums: z must live on the GPU (npe_pfn.diagnostics.mmd_sums_host is the CPU statement)")
+    z = z.to(torch.float32).contiguous()
+    labels = torch.as_tensor(labels)
+    code, bw = check_mmd_args(z.shape, labels.shape, kernel, bandwidths)
+    labels = (labels != 0).to(device=z.device, dtype=torch.uint8).contiguous()
+    n_obs, N, dim = z.shape
+    P = labels.shape[0]
+    sums = torch.empty((n_obs, P, 2), dtype=torch.int64, device=z.device)
+    total = torch.empty((n_obs,), dtype=torch.int64, device=z.device)
+    bad = torch.empty((n_obs,), dtype=torch.int32, device=z.device)
+    lib = lib or load_library()
+    host_bw = (ctypes.c_float * len(bw))(*bw)
+    with torch.cuda.device(z.device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(z.device).cuda_stream)
+        _check(lib, lib.npfn_mmd_sums(_ptr(z), n_obs, N, dim, code, ctypes.cast(host_bw, _vp), len(bw), _ptr(labels),
+                                      P, _ptr(sums), _ptr(total),
+                                      ctypes.cast(ctypes.c_void_p(bad.data_ptr()), ctypes.POINTER(_i32)), stream),
+               "npfn_mmd_sums")
+    return sums, total, bad
 
 
 MAX_QUANTILES = 64  # npfn_bar_stats / npfn_predict_stats take at most this many levels per call
@@ -798,6 +856,16 @@ class Engine:
         _check(self.lib, self.lib.npfn_pair_accumulate(
             _ptr(w), _ptr(theta), ldt, n_prev, _ptr(edges), G, r0, n, per, _ptr(pairQ), _ptr(cellQ),
             ctypes.cast(ctypes.c_void_p(bad.data_ptr()), ctypes.POINTER(_i32)), self.stream), "npfn_pair_accumulate")
+
+    # ------------------------------------------------- MMD two-sample sums (npfn_mmd.hip)
+    def mmd_sums(self, z, labels, kernel, bandwidths) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """npfn_mmd_sums on the engine's device and stream: :func:`mmd_sums` of this module (the
+        entry point needs no engine state; ``z`` and ``labels`` are moved to the engine's device).
+        ValueError for arguments that do not fit, before the C call."""
+        z = torch.as_tensor(z)
+        labels = torch.as_tensor(labels)
+        check_mmd_args(z.shape, labels.shape, kernel, bandwidths)
+        return mmd_sums(z.to(self.device), labels.to(self.device), kernel, bandwidths, lib=self.lib)
 
     def filter_stdeuclid(self, x: torch.Tensor, obs: torch.Tensor, k: int) -> torch.Tensor:
         x = _dev_f32(x, self.device)

@@ -29,7 +29,7 @@ from torch import Tensor
 from torch.distributions import Distribution
 
 from .accept_reject_sampler import accept_reject_sample
-from .diagnostics import CoverageRanks, bar_cdf, rank_accumulate_host
+from .diagnostics import CoverageRanks, TwoSampleResult, bar_cdf, mmd_batched, rank_accumulate_host
 from .kmeans import KMeansState
 from .marginals import PosteriorMarginals
 from .pair_marginals import MAX_PER as PAIR_MAX_PER
@@ -543,6 +543,28 @@ class NPE_PFN_Core:
             raise RuntimeError(f"coverage_batched: {int((need > 0).sum())} observation(s) got fewer than {n} samples "
                                "inside the prior support after 10 rounds")
         return counts, lp_true, out_th, out_lp
+
+    def mmd_batched(self, theta_ref: Tensor, x: Tensor, num_posterior_samples: Optional[int] = None,
+                    **kw) -> TwoSampleResult:
+        """MMD two-sample test of this estimator's draws against reference draws, observation by
+        observation: ``theta_ref`` [M, T, d_theta] are the reference draws (a ground-truth
+        posterior, another estimator, another seed) for ``x`` [M, dx].  Draws
+        ``num_posterior_samples`` (default T) per observation with :meth:`sample_batched` -- the
+        sample counter advances as that call advances it -- and returns
+        :func:`npe_pfn.diagnostics.mmd_batched` ``(draws, theta_ref, **kw)``: ``kernel``,
+        ``bandwidths``, ``num_permutations``, ``seed`` and ``z_score`` are its arguments."""
+        theta_ref = torch.as_tensor(theta_ref)
+        n_obs = 1 if torch.as_tensor(x).ndim < 2 else x.shape[0]
+        dth = self._theta_train.shape[1]
+        if theta_ref.ndim != 3 or theta_ref.shape[0] != n_obs or theta_ref.shape[1] < 1 or theta_ref.shape[2] != dth:
+            raise ValueError(f"mmd_batched: theta_ref {tuple(theta_ref.shape)} is not [{n_obs}, T >= 1, {dth}] (the "
+                             "reference draws of every row of x)")
+        n = theta_ref.shape[1] if num_posterior_samples is None else int(num_posterior_samples)
+        if n < 1:
+            raise ValueError(f"mmd_batched: num_posterior_samples ({n}) must be >= 1")
+        draws = self.sample_batched(x, (n,))
+        engine = self._model.engine if self._fused() and draws.device.type == "cuda" else None
+        return mmd_batched(draws, theta_ref.to(draws.device), engine=engine, **kw)
 
     def pit_batched(self, theta: Tensor, x: Tensor) -> Tensor:
         """Per-dimension probability integral transform u_k = F_k(theta_k | x, theta_<k) of the
@@ -1120,6 +1142,12 @@ class TabPFN_Based_Uncond_Estimator(NPE_PFN_Core):
         """Not provided, for the reason given at :meth:`log_prob_batched`."""
         raise NotImplementedError("TabPFN_Based_Uncond_Estimator has no observations to batch over (its x is a "
                                   "dummy column); use log_prob(theta)")
+
+    def mmd_batched(self, theta_ref: Tensor, x: Tensor = None, *args, **kwargs):
+        """Not provided, for the reason given at :meth:`log_prob_batched`; compare draws of
+        :meth:`sample` with :func:`npe_pfn.diagnostics.mmd_batched`."""
+        raise NotImplementedError("TabPFN_Based_Uncond_Estimator has no observations to batch over (its x is a "
+                                  "dummy column); call npe_pfn.diagnostics.mmd_batched on sample()'s draws")
 
     def log_prob(self, theta: Tensor, x: Tensor = None, max_sampling_batch_size: int = 10_000,
                  mode: str = "autoregressive", eps: float = 1e-15, **ratio_kwargs) -> Tensor:
