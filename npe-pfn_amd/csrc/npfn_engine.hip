@@ -1164,23 +1164,6 @@ int check_engine(npfn_engine* h) {
   return NPFN_OK;
 }
 
-// per > 1: xq holds N / per distinct rows, query row i = xq[i / per] (npfn_ar_sample_repeated)
-int ar_common_setup(npfn_engine* h, const float* x_ctx, const float* theta_ctx, int64_t n, int dx, int dth,
-                    const float* xq, int64_t N, hipStream_t s, int64_t per = 1) {
-  if (!x_ctx || !theta_ctx || !xq) return fail(NPFN_EINVAL, "ar: null input");
-  if (dx < 1 || dth < 1 || n < 1 || N < 0) return fail(NPFN_EINVAL, "ar: bad dimensions");
-  const int Ft = dx + dth;
-  RCHK(order_after_last_call(h, s));
-  RCHK(ensure(h->joint, (size_t)n * Ft * sizeof(float), s));
-  RCHK(ensure(h->feat, (size_t)std::max<int64_t>(N, 1) * Ft * sizeof(float), s));
-  RCHK(ensure(h->logp, (size_t)std::max<int64_t>(N, 1) * sizeof(float), s));
-  launch_copy_cols(x_ctx, dx, (float*)h->joint.p, Ft, n, dx, 0, s);
-  launch_copy_cols(theta_ctx, dth, (float*)h->joint.p, Ft, n, dth, dx, s);
-  launch_copy_cols(xq, dx, (float*)h->feat.p, Ft, N, dx, 0, s, per);
-  launch_fill((float*)h->logp.p, N, 0.f, s);
-  return NPFN_OK;
-}
-
 // ---------------------------------------------------------------- fit cache
 // Everything a fit reads from the engine besides the context table: the table's shape, the
 // preprocessing (mode, regressor / classifier pipelines, quantile divisor) and the estimator
@@ -1501,251 +1484,273 @@ int ar_step_fit(npfn_engine* h, const float* joint, int Ft, int64_t n, int dx, i
   return NPFN_OK;
 }
 
-// npfn_ar_sample (n_unique = 0: x_query [n_rows][dim_x]) and npfn_ar_sample_repeated
-// (x_query [n_unique][dim_x], query row i = x_query[i / (n_rows / n_unique)]).  With repeated
+// Every AR call is one pass of ar_run over the steps k = 0 .. dim_theta - 1: the call's setup and
+// fits, per step the step's fit and the forward of every chunk of h->chunk_rows rows, whose
+// logits go to the call's step consumer.  n_unique = 0: x_query [n_rows][dim_x]; else x_query
+// [n_unique][dim_x] and query row i = x_query[i / per], per = n_rows / n_unique.  With repeated
 // rows, step 0 -- whose features are the query rows alone -- runs the forward, decoder and
-// ensemble mix once per distinct row and every draw samples from its row's mixture
-// (k_group_sample); steps >= 1 see distinct sampled columns and run over every row.
-// npfn_ar_marginals (marg_out / borders_out set, n_unique >= 1): every step's row mixtures also
-// pass through the window margwin -- k_mix_prob writes a chunk's masses, k_group_sample with
-// per = 1 draws from them (k_mix_sample's draw, bit for bit) and launch_marg_accum adds them to
-// the observations' sums; step 0's marginal is the distinct row's own mixture.
-// npfn_ar_pair_marginals (po set, n_unique >= 1) takes the same window route: every window's
-// mixtures are re-binned onto the step's G cells (launch_bar_cell_mass) and folded, keyed by the
-// cells of the rows' earlier draws, into the step's integer tables (launch_pair_accumulate),
-// which launch_pair_final turns into pair (j, k), j < k, and the cell masses of dimension k.
-struct PairOut {
-  const float* edges;  // [dim_theta][G + 1]
-  int G;
-  float* pair_out;     // [n_unique][dim_theta (dim_theta - 1) / 2][G][G]
-  float* cell_out;     // [n_unique][dim_theta][G]
+// ensemble mix (k_mix_prob) once per distinct row into h->pu, and the consumer serves every row
+// from its row's mixture (k_group_*); steps >= 1 see distinct columns and run over every row.
+// A step consumer is a plain struct with kName (for need_full_range), kProf (the category of step
+// 0's mix) and the hooks check (the call's own argument checks, first of all), begin (workspaces;
+// the teacher-forced passes fill feat), step_begin (step k's fit is in h->f), step0 (repeated
+// rows: the distinct rows' mixtures are in pu), chunk (rows r0 .. r0 + rows of step k: their logits
+// are in h->logits), step_end (after step k's chunks, not after step0) and end (the copies out).
+struct ArPass {
+  npfn_engine* h;
+  hipStream_t s;
+  int dim_x, dim_theta, Ft, E, nb;
+  int64_t n_unique, n_rows, per;
+  float invT, log_eps;
+  float* feat;  // [n_rows][Ft]: the query rows, then theta's columns
+  const float* ystats() const { return (const float*)h->f->ystats.p; }
+  const logit_t* logits() const { return (const logit_t*)h->logits.p; }
+  double logit_bytes(int64_t rows) const { return (double)E * rows * nb * sizeof(logit_t); }
 };
-int ar_sample_impl(npfn_engine* h, const float* x_ctx, const float* theta_ctx, int64_t n_ctx, int dim_x,
-                   int dim_theta, const float* x_query, int64_t n_unique, int64_t n_rows, uint64_t counter,
-                   int64_t row_base, float* theta_out, float* log_prob_out, float eps, hipStream_t s,
-                   float* marg_out = nullptr, float* borders_out = nullptr, const PairOut* po = nullptr) {
-  if (!theta_out && !marg_out && !po) return fail(NPFN_EINVAL, "ar_sample: null theta_out");
-  if (row_base < 0) return fail(NPFN_EINVAL, "ar_sample: negative row_base");
-  RCHK(need_full_range(h, "ar_sample"));
+void build_joint(npfn_engine* h, const float* x_ctx, const float* theta_ctx, int64_t n, int dx, int dth, hipStream_t s) {
+  launch_copy_cols(x_ctx, dx, (float*)h->joint.p, dx + dth, n, dx, 0, s);
+  launch_copy_cols(theta_ctx, dth, (float*)h->joint.p, dx + dth, n, dth, dx, s);
+}
+template <class Step>
+int ar_run(npfn_engine* h, const float* x_ctx, const float* theta_ctx, int64_t n_ctx, int dim_x, int dim_theta,
+           const float* x_query, int64_t n_unique, int64_t n_rows, float eps, hipStream_t s, Step st) {
+  RCHK(st.check());
+  RCHK(need_full_range(h, Step::kName));
   RCHK(ensure_pipelines(h, false));
+  if (!x_ctx || !theta_ctx || !x_query) return fail(NPFN_EINVAL, "ar: null input");
+  if (dim_x < 1 || dim_theta < 1 || n_ctx < 1 || n_rows < 0) return fail(NPFN_EINVAL, "ar: bad dimensions");
   const int64_t per = n_unique > 0 ? n_rows / n_unique : 1;
-  RCHK(ar_common_setup(h, x_ctx, theta_ctx, n_ctx, dim_x, dim_theta, x_query, n_rows, s, per));
-  const int Ft = dim_x + dim_theta, E = h->cfg.n_estimators, nb = h->cfg.n_bars;
-  const float invT = 1.0f / h->cfg.softmax_temperature;
-  const float log_eps = logf(eps);
-  float* joint = (float*)h->joint.p;
-  float* feat = (float*)h->feat.p;
-  float* logp = log_prob_out ? (float*)h->logp.p : nullptr;
+  const int Ft = dim_x + dim_theta;
+  RCHK(order_after_last_call(h, s));
+  RCHK(ensure(h->joint, (size_t)n_ctx * Ft * sizeof(float), s));
+  RCHK(ensure(h->feat, (size_t)std::max<int64_t>(n_rows, 1) * Ft * sizeof(float), s));
+  RCHK(ensure(h->logp, (size_t)std::max<int64_t>(n_rows, 1) * sizeof(float), s));
+  const ArPass a{h, s, dim_x, dim_theta, Ft, h->cfg.n_estimators, h->cfg.n_bars, n_unique, n_rows, per,
+                 1.0f / h->cfg.softmax_temperature, logf(eps), (float*)h->feat.p};
+  const float* joint = (const float*)h->joint.p;
+  build_joint(h, x_ctx, theta_ctx, n_ctx, dim_x, dim_theta, s);
+  launch_copy_cols(x_query, dim_x, a.feat, Ft, n_rows, dim_x, 0, s, per);
+  launch_fill((float*)h->logp.p, n_rows, 0.f, s);
+  RCHK(st.begin(a));
   bool reuse = false, piped = false;
-  const int64_t win_rows = std::min(h->chunk_rows, n_rows);
-  if (marg_out) {
-    RCHK(ensure(h->margwin, (size_t)win_rows * nb * sizeof(float), s));
-    RCHK(ensure(h->marginv, (size_t)std::max(win_rows, n_unique) * sizeof(double), s));
-    RCHK(ensure(h->margpart, (size_t)n_unique * marg_strips(per) * nb * sizeof(double), s));
+  RCHK(begin_ar_fits(h, n_ctx, dim_x, dim_theta, s, reuse));
+  if (!reuse) RCHK(ar_prefit(h, joint, a.Ft, n_ctx, dim_x, dim_theta, s, piped));
+  for (int k = 0; k < dim_theta; ++k) {
+    h->f = step_fit(h, k);
+    if (!reuse || !h->f->fitted) RCHK(ar_step_fit(h, joint, a.Ft, n_ctx, dim_x, dim_theta, k, piped, s));
+    RCHK(st.step_begin(a, k));
+    if (k == 0 && n_unique > 0 && n_rows > 0) {
+      RCHK(ensure(h->pu, (size_t)n_unique * a.nb * sizeof(float), s));
+      float* pu = (float*)h->pu.p;
+      for (int64_t u0 = 0; u0 < n_unique; u0 += h->chunk_rows) {
+        const int64_t rows = std::min(h->chunk_rows, n_unique - u0);
+        RCHK(predict_logits_chunk(h, x_query + u0 * dim_x, dim_x, rows, s));
+        ProfGuard g(h, Step::kProf, 0.0, a.logit_bytes(rows), s);
+        launch_mix_prob(a.logits(), rows, a.E, a.nb, a.invT, h->mixtrans(), pu + u0 * a.nb, s);
+      }
+      st.step0(a, pu);
+      continue;
+    }
+    for (int64_t r0 = 0; r0 < n_rows; r0 += h->chunk_rows) {
+      const int64_t rows = std::min(h->chunk_rows, n_rows - r0);
+      RCHK(predict_logits_chunk(h, a.feat + r0 * a.Ft, a.Ft, rows, s));
+      st.chunk(a, k, r0, rows);
+    }
+    st.step_end(a, k);
   }
-  const int G = po ? po->G : 0;
-  const int64_t GG = (int64_t)G * G, n_pairs = (int64_t)dim_theta * (dim_theta - 1) / 2;
-  const size_t pair_q = (size_t)n_unique * ((size_t)std::max(dim_theta - 1, 0) * GG + G);  // int64 sums per step
+  RCHK(st.end(a));
+  RCHK(end_ar_fits(h, piped, s));
+  HIPCHK(hipGetLastError());
+  return NPFN_OK;
+}
+
+// The sampling family.  Plain (both sinks absent): k_mix_sample draws column k of every chunk
+// straight from its logits; step 0 of repeated rows draws from the distinct rows' mixtures
+// (k_group_sample).  npfn_ar_marginals (marg_out / borders_out set, n_unique >= 1): every step's
+// row mixtures also pass through the window margwin -- k_mix_prob writes a chunk's masses,
+// k_group_sample with per = 1 draws from them (k_mix_sample's draw, bit for bit) and
+// launch_marg_accum adds them to the observations' sums; step 0's marginal is the distinct row's
+// own mixture.  npfn_ar_pair_marginals (edges set, n_unique >= 1) takes the same window route:
+// every window's mixtures are re-binned onto the step's G cells (launch_bar_cell_mass) and folded,
+// keyed by the cells of the rows' earlier draws, into the step's integer tables
+// (launch_pair_accumulate), which launch_pair_final turns into pair (j, k), j < k, and the cell
+// masses of dimension k.
+struct SampleStep {
+  static constexpr const char* kName = "ar_sample";
+  static constexpr int kProf = P_MIX_SAMPLE;
+  uint64_t counter;
+  int64_t row_base;
+  float *theta_out, *log_prob_out;
+  float* marg_out = nullptr;     // the marginals sink, absent when null: [n_unique][dim_theta][n_bars]
+  float* borders_out = nullptr;  // [dim_theta][n_bars + 1]
+  const float* edges = nullptr;  // the pair-marginals sink, absent when null: [dim_theta][G + 1]
+  int G = 0;
+  float* pair_out = nullptr;     // [n_unique][dim_theta (dim_theta - 1) / 2][G][G]
+  float* cell_out = nullptr;     // [n_unique][dim_theta][G]
+  // set by begin(); the step's tables in h->pairtab: [pairQ | cellQ] int64 sums, then pbad
+  float* logp = nullptr;
+  int64_t GG = 0;
+  size_t tab_bytes = 0;
   int64_t *pairQ = nullptr, *cellQ = nullptr;
   int32_t* pbad = nullptr;
-  if (po) {
-    if (nb > cell_mass_max_bars()) return fail(NPFN_EINVAL, "ar_pair_marginals: too many bars for the re-binning");
-    RCHK(ensure(h->margwin, (size_t)win_rows * nb * sizeof(float), s));
-    RCHK(ensure(h->pairw, (size_t)std::max(win_rows, n_unique) * G * sizeof(double), s));
-    RCHK(ensure(h->pairtab, pair_q * sizeof(int64_t) + (size_t)n_unique * sizeof(int32_t), s));
-    RCHK(ensure(h->pairbd, (size_t)(nb + 1) * sizeof(float), s));
-    pairQ = (int64_t*)h->pairtab.p;
-    cellQ = pairQ + (size_t)n_unique * std::max(dim_theta - 1, 0) * GG;
-    pbad = (int32_t*)(pairQ + pair_q);
+  int check() const {
+    if (!theta_out && !marg_out && !edges) return fail(NPFN_EINVAL, "ar_sample: null theta_out");
+    return row_base < 0 ? fail(NPFN_EINVAL, "ar_sample: negative row_base") : NPFN_OK;
   }
-  RCHK(begin_ar_fits(h, n_ctx, dim_x, dim_theta, s, reuse));
-  if (!reuse) RCHK(ar_prefit(h, joint, Ft, n_ctx, dim_x, dim_theta, s, piped));
-  for (int k = 0; k < dim_theta; ++k) {
-    const int F = dim_x + k;
-    h->f = step_fit(h, k);
-    if (!reuse || !h->f->fitted) RCHK(ar_step_fit(h, joint, Ft, n_ctx, dim_x, dim_theta, k, piped, s));
-    if (marg_out) launch_borders(h->bz, (const float*)h->f->ystats.p, nb, borders_out + (int64_t)k * (nb + 1), s);
-    if (po && n_rows > 0) {  // this step's borders and zeroed tables
-      launch_borders(h->bz, (const float*)h->f->ystats.p, nb, (float*)h->pairbd.p, s);
-      HIPCHK(hipMemsetAsync(h->pairtab.p, 0, pair_q * sizeof(int64_t) + (size_t)n_unique * sizeof(int32_t), s));
-    }
-    if (k == 0 && n_unique > 0 && n_rows > 0) {
-      RCHK(ensure(h->pu, (size_t)n_unique * nb * sizeof(float), s));
-      float* pu = (float*)h->pu.p;
-      for (int64_t u0 = 0; u0 < n_unique; u0 += h->chunk_rows) {
-        const int64_t rows = std::min(h->chunk_rows, n_unique - u0);
-        RCHK(predict_logits_chunk(h, x_query + u0 * dim_x, dim_x, rows, s));
-        ProfGuard g(h, P_MIX_SAMPLE, 0.0, (double)E * rows * nb * sizeof(logit_t), s);
-        launch_mix_prob((const logit_t*)h->logits.p, rows, E, nb, invT, h->mixtrans(), pu + u0 * nb, s);
-      }
-      if (marg_out) {  // one mixture per observation: its normalised masses, no averaging
-        ProfGuard g(h, P_OTHER, 0.0, (double)n_unique * nb * 24, s);
-        launch_marg_accum(pu, 0, n_unique, 1, nb, (double*)h->marginv.p, (double*)h->margpart.p, s);
-        launch_marg_final((const double*)h->margpart.p, n_unique, 1, nb, marg_out, (int64_t)dim_theta * nb, s);
-      }
-      if (po) {  // no pairs at step 0: the distinct row's own cell masses
-        ProfGuard g(h, P_OTHER, 0.0, (double)n_unique * (nb * 4 + G * 24), s);
-        launch_bar_cell_mass(pu, (const float*)h->pairbd.p, n_unique, nb, po->edges, G, (double*)h->pairw.p, s);
-        launch_pair_accumulate((const double*)h->pairw.p, nullptr, 0, 0, nullptr, G, 0, n_unique, 1, pairQ, cellQ,
-                               pbad, s);
-        launch_pair_final(cellQ, pbad, n_unique, G, 1, po->cell_out, (int64_t)dim_theta * G, s);
-      }
-      ProfGuard g(h, P_MIX_SAMPLE, 0.0, (double)n_rows * nb * 4, s);
-      launch_group_sample(pu, per, n_rows, nb, h->bz, (const float*)h->f->ystats.p, h->cfg.random_state,
-                          counter + (uint64_t)k, 0, (uint64_t)row_base, feat, Ft, F, logp, log_eps, s);
-      continue;
-    }
-    for (int64_t r0 = 0; r0 < n_rows; r0 += h->chunk_rows) {
-      const int64_t rows = std::min(h->chunk_rows, n_rows - r0);
-      RCHK(predict_logits_chunk(h, feat + r0 * Ft, Ft, rows, s));
-      if (marg_out || po) {
-        float* win = (float*)h->margwin.p;
-        {
-          ProfGuard g(h, P_MIX_SAMPLE, 0.0, (double)E * rows * nb * sizeof(logit_t) + (double)rows * nb * 8, s);
-          launch_mix_prob((const logit_t*)h->logits.p, rows, E, nb, invT, h->mixtrans(), win, s);
-          // k_group_sample reads the mixture of row row_offset + r at p_rows[(row_offset + r) / per]:
-          // with per = 1 and the base moved back by r0 rows that is window row r (the moved base is
-          // only ever indexed from row r0 on)
-          launch_group_sample(win - r0 * nb, 1, rows, nb, h->bz, (const float*)h->f->ystats.p, h->cfg.random_state,
-                              counter + (uint64_t)k, r0, (uint64_t)row_base, feat, Ft, F, logp, log_eps, s);
-        }
-        ProfGuard g(h, P_OTHER, 0.0, (double)rows * nb * 8, s);
-        if (marg_out) launch_marg_accum(win, r0, rows, per, nb, (double*)h->marginv.p, (double*)h->margpart.p, s);
-        if (po) {  // the draws of this window are in feat by now (stream order)
-          launch_bar_cell_mass(win, (const float*)h->pairbd.p, rows, nb, po->edges + (int64_t)k * (G + 1), G,
-                               (double*)h->pairw.p, s);
-          launch_pair_accumulate((const double*)h->pairw.p, feat + r0 * Ft + dim_x, Ft, k, po->edges, G, r0, rows, per,
-                                 pairQ, cellQ, pbad, s);
-        }
-        continue;
-      }
-      ProfGuard g(h, P_MIX_SAMPLE, 0.0, (double)E * rows * nb * sizeof(logit_t), s);
-      launch_mix_sample((const logit_t*)h->logits.p, rows, E, nb, invT, h->mixtrans(), h->bz, (const float*)h->f->ystats.p,
-                        h->cfg.random_state, counter + (uint64_t)k, r0, (uint64_t)row_base, feat, Ft, F, logp,
-                        log_eps, s);
-    }
+  int begin(const ArPass& a) {
+    npfn_engine* h = a.h;
+    logp = log_prob_out ? (float*)h->logp.p : nullptr;
+    const int64_t win_rows = std::min(h->chunk_rows, a.n_rows);
     if (marg_out) {
-      ProfGuard g(h, P_OTHER, 0.0, (double)n_unique * marg_strips(per) * nb * 8, s);
-      launch_marg_final((const double*)h->margpart.p, n_unique, per, nb, marg_out + (int64_t)k * nb,
-                        (int64_t)dim_theta * nb, s);
+      RCHK(ensure(h->margwin, (size_t)win_rows * a.nb * sizeof(float), a.s));
+      RCHK(ensure(h->marginv, (size_t)std::max(win_rows, a.n_unique) * sizeof(double), a.s));
+      RCHK(ensure(h->margpart, (size_t)a.n_unique * marg_strips(a.per) * a.nb * sizeof(double), a.s));
     }
-    if (po) {
-      ProfGuard g(h, P_OTHER, 0.0, (double)n_unique * (k * GG + G) * 12, s);
-      launch_pair_final(pairQ, pbad, n_unique, k * GG, per, po->pair_out + (int64_t)k * (k - 1) / 2 * GG, n_pairs * GG, s);
-      launch_pair_final(cellQ, pbad, n_unique, G, per, po->cell_out + (int64_t)k * G, (int64_t)dim_theta * G, s);
+    if (edges) {
+      if (a.nb > cell_mass_max_bars()) return fail(NPFN_EINVAL, "ar_pair_marginals: too many bars for the re-binning");
+      GG = (int64_t)G * G;
+      const size_t pairs_q = (size_t)a.n_unique * std::max(a.dim_theta - 1, 0) * GG, pair_q = pairs_q + a.n_unique * G;
+      tab_bytes = pair_q * sizeof(int64_t) + (size_t)a.n_unique * sizeof(int32_t);
+      RCHK(ensure(h->margwin, (size_t)win_rows * a.nb * sizeof(float), a.s));
+      RCHK(ensure(h->pairw, (size_t)std::max(win_rows, a.n_unique) * G * sizeof(double), a.s));
+      RCHK(ensure(h->pairtab, tab_bytes, a.s));
+      RCHK(ensure(h->pairbd, (size_t)(a.nb + 1) * sizeof(float), a.s));
+      pairQ = (int64_t*)h->pairtab.p;
+      cellQ = pairQ + pairs_q;
+      pbad = (int32_t*)(pairQ + pair_q);
+    }
+    return NPFN_OK;
+  }
+  int step_begin(const ArPass& a, int k) {
+    if (marg_out) launch_borders(a.h->bz, a.ystats(), a.nb, borders_out + (int64_t)k * (a.nb + 1), a.s);
+    if (edges && a.n_rows > 0) {  // this step's borders and zeroed tables
+      launch_borders(a.h->bz, a.ystats(), a.nb, (float*)a.h->pairbd.p, a.s);
+      HIPCHK(hipMemsetAsync(a.h->pairtab.p, 0, tab_bytes, a.s));
+    }
+    return NPFN_OK;
+  }
+  // draws column k of rows r0 .. r0 + rows from the mixtures p_rows[row / per]
+  void group_sample(const ArPass& a, int k, const float* p_rows, int64_t per, int64_t r0, int64_t rows) {
+    launch_group_sample(p_rows, per, rows, a.nb, a.h->bz, a.ystats(), a.h->cfg.random_state, counter + (uint64_t)k, r0,
+                        (uint64_t)row_base, a.feat, a.Ft, a.dim_x + k, logp, a.log_eps, a.s);
+  }
+  void step0(const ArPass& a, const float* pu) {
+    npfn_engine* h = a.h;
+    if (marg_out) {  // one mixture per observation: its normalised masses, no averaging
+      ProfGuard g(h, P_OTHER, 0.0, (double)a.n_unique * a.nb * 24, a.s);
+      launch_marg_accum(pu, 0, a.n_unique, 1, a.nb, (double*)h->marginv.p, (double*)h->margpart.p, a.s);
+      launch_marg_final((const double*)h->margpart.p, a.n_unique, 1, a.nb, marg_out, (int64_t)a.dim_theta * a.nb, a.s);
+    }
+    if (edges) {  // no pairs at step 0: the distinct row's own cell masses
+      ProfGuard g(h, P_OTHER, 0.0, (double)a.n_unique * (a.nb * 4 + G * 24), a.s);
+      launch_bar_cell_mass(pu, (const float*)h->pairbd.p, a.n_unique, a.nb, edges, G, (double*)h->pairw.p, a.s);
+      launch_pair_accumulate((const double*)h->pairw.p, nullptr, 0, 0, nullptr, G, 0, a.n_unique, 1, pairQ, cellQ, pbad,
+                             a.s);
+      launch_pair_final(cellQ, pbad, a.n_unique, G, 1, cell_out, (int64_t)a.dim_theta * G, a.s);
+    }
+    ProfGuard g(h, P_MIX_SAMPLE, 0.0, (double)a.n_rows * a.nb * 4, a.s);
+    group_sample(a, 0, pu, a.per, 0, a.n_rows);
+  }
+  void chunk(const ArPass& a, int k, int64_t r0, int64_t rows) {
+    npfn_engine* h = a.h;
+    if (!marg_out && !edges) {
+      ProfGuard g(h, P_MIX_SAMPLE, 0.0, a.logit_bytes(rows), a.s);
+      launch_mix_sample(a.logits(), rows, a.E, a.nb, a.invT, h->mixtrans(), h->bz, a.ystats(), h->cfg.random_state,
+                        counter + (uint64_t)k, r0, (uint64_t)row_base, a.feat, a.Ft, a.dim_x + k, logp, a.log_eps, a.s);
+      return;
+    }
+    float* win = (float*)h->margwin.p;
+    {
+      ProfGuard g(h, P_MIX_SAMPLE, 0.0, a.logit_bytes(rows) + (double)rows * a.nb * 8, a.s);
+      launch_mix_prob(a.logits(), rows, a.E, a.nb, a.invT, h->mixtrans(), win, a.s);
+      // k_group_sample reads the mixture of row row_offset + r at p_rows[(row_offset + r) / per]:
+      // with per = 1 and the base moved back by r0 rows that is window row r (the moved base is
+      // only ever indexed from row r0 on)
+      group_sample(a, k, win - r0 * a.nb, 1, r0, rows);
+    }
+    ProfGuard g(h, P_OTHER, 0.0, (double)rows * a.nb * 8, a.s);
+    if (marg_out) launch_marg_accum(win, r0, rows, a.per, a.nb, (double*)h->marginv.p, (double*)h->margpart.p, a.s);
+    if (edges) {  // the draws of this window are in feat by now (stream order)
+      launch_bar_cell_mass(win, (const float*)h->pairbd.p, rows, a.nb, edges + (int64_t)k * (G + 1), G,
+                           (double*)h->pairw.p, a.s);
+      launch_pair_accumulate((const double*)h->pairw.p, a.feat + r0 * a.Ft + a.dim_x, a.Ft, k, edges, G, r0, rows, a.per,
+                             pairQ, cellQ, pbad, a.s);
     }
   }
-  if (theta_out) launch_copy_cols(feat + dim_x, Ft, theta_out, dim_theta, n_rows, dim_theta, 0, s);
-  if (log_prob_out && n_rows > 0)
-    HIPCHK(hipMemcpyAsync(log_prob_out, h->logp.p, n_rows * sizeof(float), hipMemcpyDeviceToDevice, s));
-  RCHK(end_ar_fits(h, piped, s));
-  HIPCHK(hipGetLastError());
-  return NPFN_OK;
-}
+  void step_end(const ArPass& a, int k) {
+    if (marg_out) {
+      ProfGuard g(a.h, P_OTHER, 0.0, (double)a.n_unique * marg_strips(a.per) * a.nb * 8, a.s);
+      launch_marg_final((const double*)a.h->margpart.p, a.n_unique, a.per, a.nb, marg_out + (int64_t)k * a.nb,
+                        (int64_t)a.dim_theta * a.nb, a.s);
+    }
+    if (edges) {
+      const int64_t n_pairs = (int64_t)a.dim_theta * (a.dim_theta - 1) / 2;
+      ProfGuard g(a.h, P_OTHER, 0.0, (double)a.n_unique * (k * GG + G) * 12, a.s);
+      launch_pair_final(pairQ, pbad, a.n_unique, k * GG, a.per, pair_out + (int64_t)k * (k - 1) / 2 * GG, n_pairs * GG, a.s);
+      launch_pair_final(cellQ, pbad, a.n_unique, G, a.per, cell_out + (int64_t)k * G, (int64_t)a.dim_theta * G, a.s);
+    }
+  }
+  int end(const ArPass& a) {
+    if (theta_out) launch_copy_cols(a.feat + a.dim_x, a.Ft, theta_out, a.dim_theta, a.n_rows, a.dim_theta, 0, a.s);
+    if (log_prob_out && a.n_rows > 0)
+      HIPCHK(hipMemcpyAsync(log_prob_out, a.h->logp.p, a.n_rows * sizeof(float), hipMemcpyDeviceToDevice, a.s));
+    return NPFN_OK;
+  }
+};
 
-// npfn_ar_log_prob (n_unique = 0) and npfn_ar_log_prob_repeated: step 0 once per distinct query
-// row (k_mix_prob), every row's log density of its own theta from its row's mixture (k_group_nll).
-int ar_log_prob_impl(npfn_engine* h, const float* x_ctx, const float* theta_ctx, int64_t n_ctx, int dim_x,
-                     int dim_theta, const float* x_query, int64_t n_unique, const float* theta, int64_t n_rows,
-                     float* log_prob_out, float eps, hipStream_t s) {
-  if (!theta || !log_prob_out) return fail(NPFN_EINVAL, "ar_log_prob: null pointer");
-  RCHK(need_full_range(h, "ar_log_prob"));
-  RCHK(ensure_pipelines(h, false));
-  const int64_t per = n_unique > 0 ? n_rows / n_unique : 1;
-  RCHK(ar_common_setup(h, x_ctx, theta_ctx, n_ctx, dim_x, dim_theta, x_query, n_rows, s, per));
-  const int Ft = dim_x + dim_theta, E = h->cfg.n_estimators, nb = h->cfg.n_bars;
-  const float invT = 1.0f / h->cfg.softmax_temperature;
-  const float log_eps = logf(eps);
-  float* joint = (float*)h->joint.p;
-  float* feat = (float*)h->feat.p;
-  launch_copy_cols(theta, dim_theta, feat, Ft, n_rows, dim_theta, dim_x, s);
-  bool reuse = false, piped = false;
-  RCHK(begin_ar_fits(h, n_ctx, dim_x, dim_theta, s, reuse));
-  if (!reuse) RCHK(ar_prefit(h, joint, Ft, n_ctx, dim_x, dim_theta, s, piped));
-  for (int k = 0; k < dim_theta; ++k) {
-    const int F = dim_x + k;
-    h->f = step_fit(h, k);
-    if (!reuse || !h->f->fitted) RCHK(ar_step_fit(h, joint, Ft, n_ctx, dim_x, dim_theta, k, piped, s));
-    if (k == 0 && n_unique > 0 && n_rows > 0) {
-      RCHK(ensure(h->pu, (size_t)n_unique * nb * sizeof(float), s));
-      float* pu = (float*)h->pu.p;
-      for (int64_t u0 = 0; u0 < n_unique; u0 += h->chunk_rows) {
-        const int64_t rows = std::min(h->chunk_rows, n_unique - u0);
-        RCHK(predict_logits_chunk(h, x_query + u0 * dim_x, dim_x, rows, s));
-        ProfGuard g(h, P_MIX_NLL, 0.0, (double)E * rows * nb * sizeof(logit_t), s);
-        launch_mix_prob((const logit_t*)h->logits.p, rows, E, nb, invT, h->mixtrans(), pu + u0 * nb, s);
-      }
-      ProfGuard g(h, P_MIX_NLL, 0.0, (double)n_rows * nb * 4, s);
-      launch_group_nll(pu, per, n_rows, nb, h->bz, (const float*)h->f->ystats.p, 0, feat, Ft, F, (float*)h->logp.p,
-                       log_eps, s);
-      continue;
-    }
-    for (int64_t r0 = 0; r0 < n_rows; r0 += h->chunk_rows) {
-      const int64_t rows = std::min(h->chunk_rows, n_rows - r0);
-      RCHK(predict_logits_chunk(h, feat + r0 * Ft, Ft, rows, s));
-      ProfGuard g(h, P_MIX_NLL, 0.0, (double)E * rows * nb * sizeof(logit_t), s);
-      launch_mix_nll((const logit_t*)h->logits.p, rows, E, nb, invT, h->mixtrans(), h->bz, (const float*)h->f->ystats.p, r0, feat,
-                     Ft, F, (float*)h->logp.p, log_eps, s);
-    }
+// The teacher-forced passes: theta's columns are given, so every step scores column k of feat.
+// NllStep (npfn_ar_log_prob, _repeated): every row's log density of its own theta, summed over the
+// steps in h->logp and copied to lp (k_mix_nll; step 0 of repeated rows from its row's mixture,
+// k_group_nll).  ScoreStep (npfn_ar_score): the same pass with every step's log density and CDF
+// written to column k of lp / cdf [n_rows][dim_theta] (k_mix_score / k_group_score), not summed.
+template <bool kSteps>
+struct TeacherStep {
+  static constexpr const char* kName = kSteps ? "ar_score" : "ar_log_prob";
+  static constexpr int kProf = P_MIX_NLL;
+  const float* theta;
+  float *lp, *cdf;
+  int check() const {
+    if (!kSteps) return !theta || !lp ? fail(NPFN_EINVAL, "ar_log_prob: null pointer") : NPFN_OK;
+    if (!theta) return fail(NPFN_EINVAL, "ar_score: null theta");
+    return !lp && !cdf ? fail(NPFN_EINVAL, "ar_score: both outputs are null") : NPFN_OK;
   }
-  if (n_rows > 0)
-    HIPCHK(hipMemcpyAsync(log_prob_out, h->logp.p, n_rows * sizeof(float), hipMemcpyDeviceToDevice, s));
-  RCHK(end_ar_fits(h, piped, s));
-  HIPCHK(hipGetLastError());
-  return NPFN_OK;
-}
+  int begin(const ArPass& a) {
+    launch_copy_cols(theta, a.dim_theta, a.feat, a.Ft, a.n_rows, a.dim_theta, a.dim_x, a.s);
+    return NPFN_OK;
+  }
+  int step_begin(const ArPass&, int) { return NPFN_OK; }
+  // column k of rows r0 .. r0 + rows: from the chunk's logits, or (pu set) from the mixtures pu[row / per]
+  void chunk(const ArPass& a, int k, int64_t r0, int64_t rows, const float* pu = nullptr) {
+    npfn_engine* h = a.h;
+    float* acc = (float*)h->logp.p;
+    const int col = a.dim_x + k;
+    ProfGuard g(h, P_MIX_NLL, 0.0, pu ? (double)rows * a.nb * 4 : a.logit_bytes(rows), a.s);
+    if (!kSteps && pu) launch_group_nll(pu, a.per, rows, a.nb, h->bz, a.ystats(), r0, a.feat, a.Ft, col, acc, a.log_eps, a.s);
+    else if (!kSteps)
+      launch_mix_nll(a.logits(), rows, a.E, a.nb, a.invT, h->mixtrans(), h->bz, a.ystats(), r0, a.feat, a.Ft, col, acc,
+                     a.log_eps, a.s);
+    else if (pu)
+      launch_group_score(pu, a.per, rows, a.nb, h->bz, a.ystats(), r0, a.feat, a.Ft, col, lp ? lp + k : nullptr,
+                         cdf ? cdf + k : nullptr, a.dim_theta, a.log_eps, a.s);
+    else
+      launch_mix_score(a.logits(), rows, a.E, a.nb, a.invT, h->mixtrans(), h->bz, a.ystats(), r0, a.feat, a.Ft, col,
+                       lp ? lp + k : nullptr, cdf ? cdf + k : nullptr, a.dim_theta, a.log_eps, a.s);
+  }
+  void step0(const ArPass& a, const float* pu) { chunk(a, 0, 0, a.n_rows, pu); }
+  void step_end(const ArPass&, int) {}
+  int end(const ArPass& a) {
+    if (kSteps || a.n_rows <= 0) return NPFN_OK;
+    HIPCHK(hipMemcpyAsync(lp, a.h->logp.p, a.n_rows * sizeof(float), hipMemcpyDeviceToDevice, a.s));
+    return NPFN_OK;
+  }
+};
+using NllStep = TeacherStep<false>;
+using ScoreStep = TeacherStep<true>;
 
-// npfn_ar_score: ar_log_prob_impl's teacher-forced pass (n_unique = 0: x_query [n_rows][dim_x];
-// else the repeated rows' path) with every step's log density and CDF written to column k of
-// logp_steps / cdf_steps [n_rows][dim_theta] (k_mix_score / k_group_score) instead of summed.
-int ar_score_impl(npfn_engine* h, const float* x_ctx, const float* theta_ctx, int64_t n_ctx, int dim_x, int dim_theta,
-                  const float* x_query, int64_t n_unique, const float* theta, int64_t n_rows, float* logp_steps,
-                  float* cdf_steps, float eps, hipStream_t s) {
-  if (!theta) return fail(NPFN_EINVAL, "ar_score: null theta");
-  if (!logp_steps && !cdf_steps) return fail(NPFN_EINVAL, "ar_score: both outputs are null");
-  RCHK(need_full_range(h, "ar_score"));
-  RCHK(ensure_pipelines(h, false));
-  const int64_t per = n_unique > 0 ? n_rows / n_unique : 1;
-  RCHK(ar_common_setup(h, x_ctx, theta_ctx, n_ctx, dim_x, dim_theta, x_query, n_rows, s, per));
-  const int Ft = dim_x + dim_theta, E = h->cfg.n_estimators, nb = h->cfg.n_bars;
-  const float invT = 1.0f / h->cfg.softmax_temperature;
-  const float log_eps = logf(eps);
-  float* joint = (float*)h->joint.p;
-  float* feat = (float*)h->feat.p;
-  launch_copy_cols(theta, dim_theta, feat, Ft, n_rows, dim_theta, dim_x, s);
-  bool reuse = false, piped = false;
-  RCHK(begin_ar_fits(h, n_ctx, dim_x, dim_theta, s, reuse));
-  if (!reuse) RCHK(ar_prefit(h, joint, Ft, n_ctx, dim_x, dim_theta, s, piped));
-  for (int k = 0; k < dim_theta; ++k) {
-    const int F = dim_x + k;
-    float* lpk = logp_steps ? logp_steps + k : nullptr;
-    float* cdk = cdf_steps ? cdf_steps + k : nullptr;
-    h->f = step_fit(h, k);
-    if (!reuse || !h->f->fitted) RCHK(ar_step_fit(h, joint, Ft, n_ctx, dim_x, dim_theta, k, piped, s));
-    if (k == 0 && n_unique > 0 && n_rows > 0) {
-      RCHK(ensure(h->pu, (size_t)n_unique * nb * sizeof(float), s));
-      float* pu = (float*)h->pu.p;
-      for (int64_t u0 = 0; u0 < n_unique; u0 += h->chunk_rows) {
-        const int64_t rows = std::min(h->chunk_rows, n_unique - u0);
-        RCHK(predict_logits_chunk(h, x_query + u0 * dim_x, dim_x, rows, s));
-        ProfGuard g(h, P_MIX_NLL, 0.0, (double)E * rows * nb * sizeof(logit_t), s);
-        launch_mix_prob((const logit_t*)h->logits.p, rows, E, nb, invT, h->mixtrans(), pu + u0 * nb, s);
-      }
-      ProfGuard g(h, P_MIX_NLL, 0.0, (double)n_rows * nb * 4, s);
-      launch_group_score(pu, per, n_rows, nb, h->bz, (const float*)h->f->ystats.p, 0, feat, Ft, F, lpk, cdk, dim_theta,
-                         log_eps, s);
-      continue;
-    }
-    for (int64_t r0 = 0; r0 < n_rows; r0 += h->chunk_rows) {
-      const int64_t rows = std::min(h->chunk_rows, n_rows - r0);
-      RCHK(predict_logits_chunk(h, feat + r0 * Ft, Ft, rows, s));
-      ProfGuard g(h, P_MIX_NLL, 0.0, (double)E * rows * nb * sizeof(logit_t), s);
-      launch_mix_score((const logit_t*)h->logits.p, rows, E, nb, invT, h->mixtrans(), h->bz, (const float*)h->f->ystats.p, r0,
-                       feat, Ft, F, lpk, cdk, dim_theta, log_eps, s);
-    }
-  }
-  RCHK(end_ar_fits(h, piped, s));
-  HIPCHK(hipGetLastError());
+// The repeated-rows entry points' check; at_least: also n_rows >= n_unique (one row per observation to average)
+int check_repeats(const char* what, int64_t n_unique, int64_t n_rows, bool at_least) {
+  if (n_unique < 1 || n_rows < (at_least ? n_unique : 0) || n_rows % n_unique != 0)
+    return fail(NPFN_EINVAL, std::string(what) + ": need n_unique >= 1 dividing n_rows" + (at_least ? " >= n_unique" : ""));
   return NPFN_OK;
 }
 
@@ -2103,8 +2108,8 @@ int npfn_ar_sample(npfn_engine* h, const float* x_ctx, const float* theta_ctx, i
                    int32_t dim_theta, const float* x_query, int64_t n_rows, uint64_t counter, int64_t row_base,
                    float* theta_out, float* log_prob_out, float eps, void* stream) {
   RCHK(check_engine(h));
-  return ar_sample_impl(h, x_ctx, theta_ctx, n_ctx, dim_x, dim_theta, x_query, 0, n_rows, counter, row_base,
-                        theta_out, log_prob_out, eps, (hipStream_t)stream);
+  return ar_run(h, x_ctx, theta_ctx, n_ctx, dim_x, dim_theta, x_query, 0, n_rows, eps, (hipStream_t)stream,
+                SampleStep{counter, row_base, theta_out, log_prob_out});
 }
 
 int npfn_ar_sample_repeated(npfn_engine* h, const float* x_ctx, const float* theta_ctx, int64_t n_ctx, int32_t dim_x,
@@ -2112,10 +2117,9 @@ int npfn_ar_sample_repeated(npfn_engine* h, const float* x_ctx, const float* the
                             uint64_t counter, int64_t row_base, float* theta_out, float* log_prob_out, float eps,
                             void* stream) {
   RCHK(check_engine(h));
-  if (n_unique < 1 || n_rows < 0 || n_rows % n_unique != 0)
-    return fail(NPFN_EINVAL, "ar_sample_repeated: need n_unique >= 1 dividing n_rows");
-  return ar_sample_impl(h, x_ctx, theta_ctx, n_ctx, dim_x, dim_theta, x_unique, n_unique, n_rows, counter, row_base,
-                        theta_out, log_prob_out, eps, (hipStream_t)stream);
+  RCHK(check_repeats("ar_sample_repeated", n_unique, n_rows, false));
+  return ar_run(h, x_ctx, theta_ctx, n_ctx, dim_x, dim_theta, x_unique, n_unique, n_rows, eps, (hipStream_t)stream,
+                SampleStep{counter, row_base, theta_out, log_prob_out});
 }
 
 int npfn_ar_marginals(npfn_engine* h, const float* x_ctx, const float* theta_ctx, int64_t n_ctx, int32_t dim_x,
@@ -2123,12 +2127,11 @@ int npfn_ar_marginals(npfn_engine* h, const float* x_ctx, const float* theta_ctx
                       int64_t row_base, float* theta_out, float* log_prob_out, float eps, float* marg_out,
                       float* borders_out, void* stream) {
   // host checks first: they answer without an engine or a device
-  if (n_unique < 1 || n_rows < n_unique || n_rows % n_unique != 0)
-    return fail(NPFN_EINVAL, "ar_marginals: need n_unique >= 1 dividing n_rows >= n_unique");
+  RCHK(check_repeats("ar_marginals", n_unique, n_rows, true));
   if (!marg_out || !borders_out) return fail(NPFN_EINVAL, "ar_marginals: null marg_out or borders_out");
   RCHK(check_engine(h));
-  return ar_sample_impl(h, x_ctx, theta_ctx, n_ctx, dim_x, dim_theta, x_unique, n_unique, n_rows, counter, row_base,
-                        theta_out, log_prob_out, eps, (hipStream_t)stream, marg_out, borders_out);
+  return ar_run(h, x_ctx, theta_ctx, n_ctx, dim_x, dim_theta, x_unique, n_unique, n_rows, eps, (hipStream_t)stream,
+                SampleStep{counter, row_base, theta_out, log_prob_out, marg_out, borders_out});
 }
 
 int npfn_ar_pair_marginals(npfn_engine* h, const float* x_ctx, const float* theta_ctx, int64_t n_ctx, int32_t dim_x,
@@ -2136,44 +2139,41 @@ int npfn_ar_pair_marginals(npfn_engine* h, const float* x_ctx, const float* thet
                            uint64_t counter, int64_t row_base, float* theta_out, float* log_prob_out, float eps,
                            const float* edges, int32_t n_cells, float* pair_out, float* cell_out, void* stream) {
   // host checks first: they answer without an engine or a device
-  if (n_unique < 1 || n_rows < n_unique || n_rows % n_unique != 0)
-    return fail(NPFN_EINVAL, "ar_pair_marginals: need n_unique >= 1 dividing n_rows >= n_unique");
+  RCHK(check_repeats("ar_pair_marginals", n_unique, n_rows, true));
   RCHK(pair_check_cells(n_cells, n_rows / n_unique, "ar_pair_marginals"));
   if (!edges || !cell_out || (!pair_out && dim_theta > 1))
     return fail(NPFN_EINVAL, "ar_pair_marginals: null edges, pair_out or cell_out");
   RCHK(check_engine(h));
-  const PairOut po{edges, n_cells, pair_out, cell_out};
-  return ar_sample_impl(h, x_ctx, theta_ctx, n_ctx, dim_x, dim_theta, x_unique, n_unique, n_rows, counter, row_base,
-                        theta_out, log_prob_out, eps, (hipStream_t)stream, nullptr, nullptr, &po);
+  return ar_run(h, x_ctx, theta_ctx, n_ctx, dim_x, dim_theta, x_unique, n_unique, n_rows, eps, (hipStream_t)stream,
+                SampleStep{counter, row_base, theta_out, log_prob_out, nullptr, nullptr, edges, n_cells, pair_out,
+                cell_out});
 }
 
 int npfn_ar_log_prob(npfn_engine* h, const float* x_ctx, const float* theta_ctx, int64_t n_ctx, int32_t dim_x,
                      int32_t dim_theta, const float* x_query, const float* theta, int64_t n_rows,
                      float* log_prob_out, float eps, void* stream) {
   RCHK(check_engine(h));
-  return ar_log_prob_impl(h, x_ctx, theta_ctx, n_ctx, dim_x, dim_theta, x_query, 0, theta, n_rows, log_prob_out, eps,
-                          (hipStream_t)stream);
+  return ar_run(h, x_ctx, theta_ctx, n_ctx, dim_x, dim_theta, x_query, 0, n_rows, eps, (hipStream_t)stream,
+                NllStep{theta, log_prob_out, nullptr});
 }
 
 int npfn_ar_log_prob_repeated(npfn_engine* h, const float* x_ctx, const float* theta_ctx, int64_t n_ctx,
                               int32_t dim_x, int32_t dim_theta, const float* x_unique, int64_t n_unique,
                               const float* theta, int64_t n_rows, float* log_prob_out, float eps, void* stream) {
   RCHK(check_engine(h));
-  if (n_unique < 1 || n_rows < 0 || n_rows % n_unique != 0)
-    return fail(NPFN_EINVAL, "ar_log_prob_repeated: need n_unique >= 1 dividing n_rows");
-  return ar_log_prob_impl(h, x_ctx, theta_ctx, n_ctx, dim_x, dim_theta, x_unique, n_unique, theta, n_rows,
-                          log_prob_out, eps, (hipStream_t)stream);
+  RCHK(check_repeats("ar_log_prob_repeated", n_unique, n_rows, false));
+  return ar_run(h, x_ctx, theta_ctx, n_ctx, dim_x, dim_theta, x_unique, n_unique, n_rows, eps, (hipStream_t)stream,
+                NllStep{theta, log_prob_out, nullptr});
 }
 
 int npfn_ar_score(npfn_engine* h, const float* x_ctx, const float* theta_ctx, int64_t n_ctx, int32_t dim_x,
                   int32_t dim_theta, const float* x_unique, int64_t n_unique, const float* theta, int64_t n_rows,
                   float* logp_steps, float* cdf_steps, float eps, void* stream) {
   RCHK(check_engine(h));
-  if (n_unique < 1 || n_rows < 0 || n_rows % n_unique != 0)
-    return fail(NPFN_EINVAL, "ar_score: need n_unique >= 1 dividing n_rows");
+  RCHK(check_repeats("ar_score", n_unique, n_rows, false));
   // n_unique == n_rows: every query row is its own (npfn_ar_log_prob's path)
-  return ar_score_impl(h, x_ctx, theta_ctx, n_ctx, dim_x, dim_theta, x_unique, n_unique == n_rows ? 0 : n_unique, theta,
-                       n_rows, logp_steps, cdf_steps, eps, (hipStream_t)stream);
+  return ar_run(h, x_ctx, theta_ctx, n_ctx, dim_x, dim_theta, x_unique, n_unique == n_rows ? 0 : n_unique, n_rows, eps,
+                (hipStream_t)stream, ScoreStep{theta, logp_steps, cdf_steps});
 }
 
 int npfn_bar_cdf(const float* logits, const float* borders, const float* y, int64_t n_rows, int32_t n_bars,
@@ -2197,9 +2197,8 @@ int npfn_ar_fit_begin(npfn_engine* h, const float* x_ctx, const float* theta_ctx
   RCHK(ensure_pipelines(h, false));
   RCHK(order_after_last_call(h, s));
   RCHK(ensure(h->joint, (size_t)n_ctx * Ft * sizeof(float), s));
-  float* joint = (float*)h->joint.p;
-  launch_copy_cols(x_ctx, dim_x, joint, Ft, n_ctx, dim_x, 0, s);
-  launch_copy_cols(theta_ctx, dim_theta, joint, Ft, n_ctx, dim_theta, dim_x, s);
+  const float* joint = (const float*)h->joint.p;
+  build_joint(h, x_ctx, theta_ctx, n_ctx, dim_x, dim_theta, s);
   bool reuse = false, piped = false;
   RCHK(begin_ar_fits(h, n_ctx, dim_x, dim_theta, s, reuse));
   if (!reuse) RCHK(ar_prefit(h, joint, Ft, n_ctx, dim_x, dim_theta, s, piped));

@@ -3033,7 +3033,41 @@ __global__ __launch_bounds__(256, NPFN_MIX_MINB) void k_mix_log(const logit_t* _
   for (int b = threadIdx.x; b < nb; b += 256) out[r * ldo + b] = __logf(p[b]);
 }
 
-// Fused AR step: mix -> sample -> NLL -> write theta into the feature buffer.
+// The k_group_* kernels serve draws whose query rows repeat: row `row` takes the mixture of its
+// distinct row, p_rows[row / per] (written by k_mix_prob), loaded into the LDS slot where the
+// k_mix_* kernel of the same step leaves its own (NPFN_GROUP_SMEM_VIEW: NPFN_MIX_SMEM_VIEW's red
+// and p).  From there on each k_mix_* / k_group_* pair runs the same step_* tail on the same LDS
+// contents, so the two agree bit for bit.  (The view stays a macro in the kernel: declared inside
+// the helper it moves the register allocation of the k_mix_* <8> instances.)
+#define NPFN_GROUP_SMEM_VIEW                                                   \
+  extern __shared__ __attribute__((aligned(16))) char smem[];                 \
+  float* p = reinterpret_cast<float*>(smem + 64);                             \
+  float* red = reinterpret_cast<float*>(smem);
+__device__ __forceinline__ void group_row_load(const float* __restrict__ p_rows, int64_t per, int nb, int64_t row,
+                                               float* p) {
+  const float* src = p_rows + (row / per) * (int64_t)nb;
+  for (int b = threadIdx.x; b < nb; b += 256) p[b] = src[b];
+  __syncthreads();
+}
+
+// Sampling step of global row `row` from the LDS mixture p: draw -> NLL -> write theta into the
+// feature buffer.
+__device__ __forceinline__ void step_sample(const float* p, float* red, int64_t row, int nb,
+                                            const float* __restrict__ bz, const float* __restrict__ ystats,
+                                            uint64_t seed, uint64_t counter, uint64_t philox_row0,
+                                            float* __restrict__ feat, int64_t ldf, int col,
+                                            float* __restrict__ logp_acc, float log_eps) {
+  __shared__ float scan[256];
+  const float u = philox_uniform(seed, counter, philox_row0 + (uint64_t)row);
+  float th = 0.f, lp = 0.f;
+  bar_sample_row(p, bz, ystats[1], ystats[0], nb, u, red, scan, th, lp);
+  if (threadIdx.x == 0) {
+    feat[row * ldf + col] = th;
+    if (logp_acc != nullptr) logp_acc[row] += (lp == -INFINITY) ? log_eps : lp;
+  }
+}
+
+// Fused AR step: mix -> step_sample.
 template <int NV>  // 0: generic path, else the fast path with NV float4 per thread
 __global__ __launch_bounds__(256, NPFN_MIX_MINB) void k_mix_sample(const logit_t* __restrict__ logits, int64_t R, int E,
                                                     int nb, float invT, MixTrans tr, const float* __restrict__ bz,
@@ -3042,16 +3076,9 @@ __global__ __launch_bounds__(256, NPFN_MIX_MINB) void k_mix_sample(const logit_t
                                                     float* __restrict__ feat, int64_t ldf, int col,
                                                     float* __restrict__ logp_acc, float log_eps) {
   NPFN_MIX_SMEM_VIEW
-  __shared__ float scan[256];
   const int64_t r = blockIdx.x;
   NPFN_MIX_ROW()
-  const float u = philox_uniform(seed, counter, philox_row0 + (uint64_t)(row_offset + r));
-  float th = 0.f, lp = 0.f;
-  bar_sample_row(p, bz, ystats[1], ystats[0], nb, u, red, scan, th, lp);
-  if (threadIdx.x == 0) {
-    feat[(row_offset + r) * ldf + col] = th;
-    if (logp_acc != nullptr) logp_acc[row_offset + r] += (lp == -INFINITY) ? log_eps : lp;
-  }
+  step_sample(p, red, row_offset + r, nb, bz, ystats, seed, counter, philox_row0, feat, ldf, col, logp_acc, log_eps);
 }
 
 // Mixture p of each row (what k_mix_sample samples from), written once per distinct query row.
@@ -3064,106 +3091,20 @@ __global__ __launch_bounds__(256, NPFN_MIX_MINB) void k_mix_prob(const logit_t* 
   for (int b = threadIdx.x; b < nb; b += 256) p_out[r * nb + b] = p[b];
 }
 
-// The sampling half of k_mix_sample for draws whose query rows repeat: row r draws from the
-// mixture of its distinct row, p_rows[(row_offset + r) / per], loaded into the same LDS slot
-// k_mix_sample leaves it in, so the draw and its log density are bit for bit those of
-// k_mix_sample over the repeated rows.
+// The sampling half of k_mix_sample for draws whose query rows repeat.
 __global__ __launch_bounds__(256) void k_group_sample(const float* __restrict__ p_rows, int64_t per, int nb,
                                                       const float* __restrict__ bz, const float* __restrict__ ystats,
                                                       uint64_t seed, uint64_t counter, int64_t row_offset,
                                                       uint64_t philox_row0, float* __restrict__ feat, int64_t ldf,
                                                       int col, float* __restrict__ logp_acc, float log_eps) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* p = reinterpret_cast<float*>(smem + 64);
-  float* red = reinterpret_cast<float*>(smem);
-  __shared__ float scan[256];
+  NPFN_GROUP_SMEM_VIEW
   const int64_t r = blockIdx.x;
-  const float* src = p_rows + ((row_offset + r) / per) * (int64_t)nb;
-  for (int b = threadIdx.x; b < nb; b += 256) p[b] = src[b];
-  __syncthreads();
-  const float u = philox_uniform(seed, counter, philox_row0 + (uint64_t)(row_offset + r));
-  float th = 0.f, lp = 0.f;
-  bar_sample_row(p, bz, ystats[1], ystats[0], nb, u, red, scan, th, lp);
-  if (threadIdx.x == 0) {
-    feat[(row_offset + r) * ldf + col] = th;
-    if (logp_acc != nullptr) logp_acc[row_offset + r] += (lp == -INFINITY) ? log_eps : lp;
-  }
+  group_row_load(p_rows, per, nb, row_offset + r, p);
+  step_sample(p, red, row_offset + r, nb, bz, ystats, seed, counter, philox_row0, feat, ldf, col, logp_acc, log_eps);
 }
 
-// Full-support bar log density of th under the mixture p[0..nb) (unnormalized, divided by its
-// block sum), borders bz * bs + bsh; every thread calls it, thread 0's result is the one used.
-__device__ float bar_logp_row(const float* __restrict__ p, int nb, const float* __restrict__ bz, float bs, float bsh,
-                              float th, float* red) {
-  float tot = 0.f;
-  for (int b = threadIdx.x; b < nb; b += 256) tot += p[b];
-  tot = block_reduce_sum(tot, red);
-  if (threadIdx.x != 0) return 0.f;
-  int lo = 0, hi = nb + 1;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (bz[mid] * bs + bsh < th) lo = mid + 1; else hi = mid;
-  }
-  int j = lo - 1;
-  if (th == bz[0] * bs + bsh) j = 0;
-  if (th == bz[nb] * bs + bsh) j = nb - 1;
-  j = min(max(j, 0), nb - 1);
-  const double w = (double)(bz[j + 1] * bs + bsh) - (double)(bz[j] * bs + bsh);
-  double lp = log((double)p[j] / (double)tot) - log(w);
-  if (j == 0) {
-    const double s0 = w / NPFN_HALFNORMAL_MEDIAN;
-    const double vv = fmax((double)(bz[1] * bs + bsh) - (double)th, 1e-8);
-    lp += log(sqrt(2.0 / M_PI) / s0) - vv * vv / (2.0 * s0 * s0) + log(w);
-  }
-  if (j == nb - 1) {
-    const double s1 = w / NPFN_HALFNORMAL_MEDIAN;
-    const double vv = fmax((double)th - (double)(bz[nb - 1] * bs + bsh), 1e-8);
-    lp += log(sqrt(2.0 / M_PI) / s1) - vv * vv / (2.0 * s1 * s1) + log(w);
-  }
-  return (float)lp;
-}
-
-// Teacher-forced step: NLL of the given target column.
-template <int NV>  // 0: generic path, else the fast path with NV float4 per thread
-__global__ __launch_bounds__(256, NPFN_MIX_MINB) void k_mix_nll(const logit_t* __restrict__ logits, int64_t R, int E, int nb,
-                                                 float invT, MixTrans tr, const float* __restrict__ bz,
-                                                 const float* __restrict__ ystats, int64_t row_offset,
-                                                 const float* __restrict__ feat, int64_t ldf, int col,
-                                                 float* __restrict__ logp_acc, float log_eps) {
-  NPFN_MIX_SMEM_VIEW
-  const int64_t r = blockIdx.x;
-  NPFN_MIX_ROW()
-  const float th = feat[(row_offset + r) * ldf + col];
-  const float lpf = bar_logp_row(p, nb, bz, ystats[1], ystats[0], th, red);
-  if (threadIdx.x == 0) logp_acc[row_offset + r] += (lpf == -INFINITY) ? log_eps : lpf;
-}
-
-// k_mix_nll for repeated query rows: row r's mixture is p_rows[(row_offset + r) / per]
-// (k_mix_prob), loaded where k_mix_nll leaves it -- the same log density bit for bit.
-__global__ __launch_bounds__(256) void k_group_nll(const float* __restrict__ p_rows, int64_t per, int nb,
-                                                   const float* __restrict__ bz, const float* __restrict__ ystats,
-                                                   int64_t row_offset, const float* __restrict__ feat, int64_t ldf,
-                                                   int col, float* __restrict__ logp_acc, float log_eps) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* p = reinterpret_cast<float*>(smem + 64);
-  float* red = reinterpret_cast<float*>(smem);
-  const int64_t r = blockIdx.x;
-  const float* src = p_rows + ((row_offset + r) / per) * (int64_t)nb;
-  for (int b = threadIdx.x; b < nb; b += 256) p[b] = src[b];
-  __syncthreads();
-  const float th = feat[(row_offset + r) * ldf + col];
-  const float lpf = bar_logp_row(p, nb, bz, ystats[1], ystats[0], th, red);
-  if (threadIdx.x == 0) logp_acc[row_offset + r] += (lpf == -INFINITY) ? log_eps : lpf;
-}
-
-// CDF of the full-support bar distribution at th: the integral of the density whose log
-// bar_logp_row returns.  bar_cdf_bucket is the NLL's bucket rule (searchsorted left - 1, the two
-// end-border fix-ups, clamped; NaN lands in bar 0 and is answered by bar_cdf_finish); every thread
-// may call it.  bar_cdf_finish, one thread per row in fp64: sl / sr = the (unnormalized) mass of
-// the bars left / right of bar j, pj that of bar j; the fraction of bar j left of th is linear in
-// an inner bar, erfc / erf of the half-normal tails (scales w / NPFN_HALFNORMAL_MEDIAN, as in the
-// NLL) in the two end bars, 1 in a bar of width 0; the result is formed from the smaller side, so
-// that the upper tail is not lost to the rounding of 1 - (a long sum from the left).  NaN for a
-// NaN th or a total that is not a positive finite number; 0 / 1 at th = -inf / +inf.
+// Bucket of th among the borders bz * bs + bsh: searchsorted left - 1, the two end-border
+// fix-ups, clamped; NaN lands in bar 0.  Every thread may call it.
 __device__ __forceinline__ int bar_cdf_bucket(const float* __restrict__ bz, float bs, float bsh, int nb, float th) {
   int lo = 0, hi = nb + 1;
   while (lo < hi) {
@@ -3175,6 +3116,72 @@ __device__ __forceinline__ int bar_cdf_bucket(const float* __restrict__ bz, floa
   if (th == bz[nb] * bs + bsh) j = nb - 1;
   return min(max(j, 0), nb - 1);
 }
+// What an end bar of width w adds to the log density: the half-normal tail of scale
+// w / NPFN_HALFNORMAL_MEDIAN in place of the uniform bar, d = th's distance from the bar's inner border.
+__device__ __forceinline__ double bar_end_logterm(double w, double d) {
+  const double s0 = w / NPFN_HALFNORMAL_MEDIAN;
+  const double vv = fmax(d, 1e-8);
+  return log(sqrt(2.0 / M_PI) / s0) - vv * vv / (2.0 * s0 * s0) + log(w);
+}
+
+// Full-support bar log density of th under the mixture p[0..nb) (unnormalized, divided by its
+// block sum), borders bz * bs + bsh; every thread calls it, thread 0's result is the one used.
+__device__ float bar_logp_row(const float* __restrict__ p, int nb, const float* __restrict__ bz, float bs, float bsh,
+                              float th, float* red) {
+  float tot = 0.f;
+  for (int b = threadIdx.x; b < nb; b += 256) tot += p[b];
+  tot = block_reduce_sum(tot, red);
+  if (threadIdx.x != 0) return 0.f;
+  const int j = bar_cdf_bucket(bz, bs, bsh, nb, th);
+  const double w = (double)(bz[j + 1] * bs + bsh) - (double)(bz[j] * bs + bsh);
+  double lp = log((double)p[j] / (double)tot) - log(w);
+  if (j == 0) lp += bar_end_logterm(w, (double)(bz[1] * bs + bsh) - (double)th);
+  if (j == nb - 1) lp += bar_end_logterm(w, (double)th - (double)(bz[nb - 1] * bs + bsh));
+  return (float)lp;
+}
+
+// Teacher-forced step of global row `row`: NLL of the given target column under the LDS mixture p.
+__device__ __forceinline__ void step_nll(const float* p, float* red, int64_t row, int nb,
+                                         const float* __restrict__ bz, const float* __restrict__ ystats,
+                                         const float* __restrict__ feat, int64_t ldf, int col,
+                                         float* __restrict__ logp_acc, float log_eps) {
+  const float th = feat[row * ldf + col];
+  const float lpf = bar_logp_row(p, nb, bz, ystats[1], ystats[0], th, red);
+  if (threadIdx.x == 0) logp_acc[row] += (lpf == -INFINITY) ? log_eps : lpf;
+}
+
+// Teacher-forced step: mix -> step_nll.
+template <int NV>  // 0: generic path, else the fast path with NV float4 per thread
+__global__ __launch_bounds__(256, NPFN_MIX_MINB) void k_mix_nll(const logit_t* __restrict__ logits, int64_t R, int E, int nb,
+                                                 float invT, MixTrans tr, const float* __restrict__ bz,
+                                                 const float* __restrict__ ystats, int64_t row_offset,
+                                                 const float* __restrict__ feat, int64_t ldf, int col,
+                                                 float* __restrict__ logp_acc, float log_eps) {
+  NPFN_MIX_SMEM_VIEW
+  const int64_t r = blockIdx.x;
+  NPFN_MIX_ROW()
+  step_nll(p, red, row_offset + r, nb, bz, ystats, feat, ldf, col, logp_acc, log_eps);
+}
+
+// k_mix_nll for repeated query rows.
+__global__ __launch_bounds__(256) void k_group_nll(const float* __restrict__ p_rows, int64_t per, int nb,
+                                                   const float* __restrict__ bz, const float* __restrict__ ystats,
+                                                   int64_t row_offset, const float* __restrict__ feat, int64_t ldf,
+                                                   int col, float* __restrict__ logp_acc, float log_eps) {
+  NPFN_GROUP_SMEM_VIEW
+  const int64_t r = blockIdx.x;
+  group_row_load(p_rows, per, nb, row_offset + r, p);
+  step_nll(p, red, row_offset + r, nb, bz, ystats, feat, ldf, col, logp_acc, log_eps);
+}
+
+// CDF of the full-support bar distribution at th: the integral of the density whose log
+// bar_logp_row returns, in the bar bar_cdf_bucket gives (a NaN th, bar 0, is answered by
+// bar_cdf_finish).  bar_cdf_finish, one thread per row in fp64: sl / sr = the (unnormalized) mass of
+// the bars left / right of bar j, pj that of bar j; the fraction of bar j left of th is linear in
+// an inner bar, erfc / erf of the half-normal tails (scales w / NPFN_HALFNORMAL_MEDIAN, as in the
+// NLL) in the two end bars, 1 in a bar of width 0; the result is formed from the smaller side, so
+// that the upper tail is not lost to the rounding of 1 - (a long sum from the left).  NaN for a
+// NaN th or a total that is not a positive finite number; 0 / 1 at th = -inf / +inf.
 __device__ float bar_cdf_finish(float sl, float pj, float sr, int j, int nb, const float* __restrict__ bz, float bs,
                                 float bsh, float th) {
   const double tot = ((double)sl + (double)pj) + (double)sr;
@@ -3218,10 +3225,27 @@ __device__ float bar_cdf_row(const float* __restrict__ p, int nb, const float* _
   return bar_cdf_finish(sl, p[j], sr, j, nb, bz, bs, bsh, th);
 }
 
-// Teacher-forced step with its per-step outputs (npfn_ar_score): k_mix_nll's mixture and log
-// density (the same bar_logp_row on the same LDS mixture), written to logp_out instead of added
-// to an accumulator, and the CDF of that mixture at the target (the PIT value).  Either output
-// may be null; row r writes element (row_offset + r) * ldo of each.
+// Teacher-forced step of global row `row` with its per-step outputs (npfn_ar_score): step_nll's
+// log density (the same bar_logp_row on the same LDS mixture), written to logp_out instead of
+// added to an accumulator, and the CDF of that mixture at the target (the PIT value).  Either
+// output may be null; the row writes element row * ldo of each.
+__device__ __forceinline__ void step_score(const float* p, float* red, int64_t row, int nb,
+                                           const float* __restrict__ bz, const float* __restrict__ ystats,
+                                           const float* __restrict__ feat, int64_t ldf, int col,
+                                           float* __restrict__ logp_out, float* __restrict__ cdf_out, int64_t ldo,
+                                           float log_eps) {
+  const float th = feat[row * ldf + col];
+  if (logp_out != nullptr) {
+    const float lpf = bar_logp_row(p, nb, bz, ystats[1], ystats[0], th, red);
+    if (threadIdx.x == 0) logp_out[row * ldo] = (lpf == -INFINITY) ? log_eps : lpf;
+  }
+  if (cdf_out != nullptr) {
+    const float c = bar_cdf_row(p, nb, bz, ystats[1], ystats[0], th, red);
+    if (threadIdx.x == 0) cdf_out[row * ldo] = c;
+  }
+}
+
+// Teacher-forced step with per-step outputs: mix -> step_score.
 template <int NV>  // 0: generic path, else the fast path with NV float4 per thread
 __global__ __launch_bounds__(256, NPFN_MIX_MINB) void k_mix_score(const logit_t* __restrict__ logits, int64_t R, int E, int nb,
                                                    float invT, MixTrans tr, const float* __restrict__ bz,
@@ -3232,40 +3256,19 @@ __global__ __launch_bounds__(256, NPFN_MIX_MINB) void k_mix_score(const logit_t*
   NPFN_MIX_SMEM_VIEW
   const int64_t r = blockIdx.x;
   NPFN_MIX_ROW()
-  const float th = feat[(row_offset + r) * ldf + col];
-  if (logp_out != nullptr) {
-    const float lpf = bar_logp_row(p, nb, bz, ystats[1], ystats[0], th, red);
-    if (threadIdx.x == 0) logp_out[(row_offset + r) * ldo] = (lpf == -INFINITY) ? log_eps : lpf;
-  }
-  if (cdf_out != nullptr) {
-    const float c = bar_cdf_row(p, nb, bz, ystats[1], ystats[0], th, red);
-    if (threadIdx.x == 0) cdf_out[(row_offset + r) * ldo] = c;
-  }
+  step_score(p, red, row_offset + r, nb, bz, ystats, feat, ldf, col, logp_out, cdf_out, ldo, log_eps);
 }
 
-// k_mix_score for repeated query rows: row r's mixture is p_rows[(row_offset + r) / per]
-// (k_mix_prob), loaded where k_mix_score leaves it -- the same outputs bit for bit.
+// k_mix_score for repeated query rows.
 __global__ __launch_bounds__(256) void k_group_score(const float* __restrict__ p_rows, int64_t per, int nb,
                                                      const float* __restrict__ bz, const float* __restrict__ ystats,
                                                      int64_t row_offset, const float* __restrict__ feat, int64_t ldf,
                                                      int col, float* __restrict__ logp_out,
                                                      float* __restrict__ cdf_out, int64_t ldo, float log_eps) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* p = reinterpret_cast<float*>(smem + 64);
-  float* red = reinterpret_cast<float*>(smem);
+  NPFN_GROUP_SMEM_VIEW
   const int64_t r = blockIdx.x;
-  const float* src = p_rows + ((row_offset + r) / per) * (int64_t)nb;
-  for (int b = threadIdx.x; b < nb; b += 256) p[b] = src[b];
-  __syncthreads();
-  const float th = feat[(row_offset + r) * ldf + col];
-  if (logp_out != nullptr) {
-    const float lpf = bar_logp_row(p, nb, bz, ystats[1], ystats[0], th, red);
-    if (threadIdx.x == 0) logp_out[(row_offset + r) * ldo] = (lpf == -INFINITY) ? log_eps : lpf;
-  }
-  if (cdf_out != nullptr) {
-    const float c = bar_cdf_row(p, nb, bz, ystats[1], ystats[0], th, red);
-    if (threadIdx.x == 0) cdf_out[(row_offset + r) * ldo] = c;
-  }
+  group_row_load(p_rows, per, nb, row_offset + r, p);
+  step_score(p, red, row_offset + r, nb, bz, ystats, feat, ldf, col, logp_out, cdf_out, ldo, log_eps);
 }
 
 // Generic criterion.cdf(logits, y): softmax(logits row) -> the masses either side of y's bar
@@ -3350,27 +3353,11 @@ __global__ __launch_bounds__(256) void k_bar_nll(const float* __restrict__ logit
   s = block_reduce_sum(s, red);
   if (threadIdx.x == 0) {
     const float th = y[r];
-    int lo = 0, hi = nb + 1;
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (b[mid] < th) lo = mid + 1; else hi = mid;
-    }
-    int j = lo - 1;
-    if (th == b[0]) j = 0;
-    if (th == b[nb]) j = nb - 1;
-    j = min(max(j, 0), nb - 1);
+    const int j = bar_cdf_bucket(b, 1.0f, 0.0f, nb, th);
     const double w = (double)b[j + 1] - (double)b[j];
     double lp = ((double)lg[j] - (double)mx - log((double)s)) - log(w);
-    if (j == 0) {
-      const double s0 = w / NPFN_HALFNORMAL_MEDIAN;
-      const double vv = fmax((double)b[1] - (double)th, 1e-8);
-      lp += log(sqrt(2.0 / M_PI) / s0) - vv * vv / (2.0 * s0 * s0) + log(w);
-    }
-    if (j == nb - 1) {
-      const double s1 = w / NPFN_HALFNORMAL_MEDIAN;
-      const double vv = fmax((double)th - (double)b[nb - 1], 1e-8);
-      lp += log(sqrt(2.0 / M_PI) / s1) - vv * vv / (2.0 * s1 * s1) + log(w);
-    }
+    if (j == 0) lp += bar_end_logterm(w, (double)b[1] - (double)th);
+    if (j == nb - 1) lp += bar_end_logterm(w, (double)th - (double)b[nb - 1]);
     out[r] = (float)(-lp);
   }
 }
@@ -3875,19 +3862,19 @@ void launch_mix_prob(const logit_t* logits, int64_t R, int E, int nb, float invT
   if (R <= 0) return;
   NPFN_MIX_LAUNCH(k_mix_prob, nb, tr, s, logits, R, E, nb, invT, tr, p_out);
 }
+// k_group_*: one block per row, LDS [64 B reduction scratch | p] as in the k_mix_* kernels
+#define NPFN_GROUP_LAUNCH(KERNEL, ...) \
+  if (R > 0) hipLaunchKernelGGL(KERNEL, dim3((unsigned)R), dim3(256), 64 + (size_t)nb * 4, s, __VA_ARGS__)
 void launch_group_sample(const float* p_rows, int64_t per, int64_t R, int nb, const float* bz, const float* ystats,
                          uint64_t seed, uint64_t counter, int64_t row_offset, uint64_t philox_row0, float* feat,
                          int64_t ldf, int col, float* logp_acc, float log_eps, hipStream_t s) {
-  if (R <= 0) return;
-  hipLaunchKernelGGL(k_group_sample, dim3((unsigned)R), dim3(256), 64 + (size_t)nb * 4, s, p_rows, per, nb, bz, ystats,
-                     seed, counter, row_offset, philox_row0, feat, ldf, col, logp_acc, log_eps);
+  NPFN_GROUP_LAUNCH(k_group_sample, p_rows, per, nb, bz, ystats, seed, counter, row_offset, philox_row0, feat, ldf,
+                    col, logp_acc, log_eps);
 }
 void launch_group_nll(const float* p_rows, int64_t per, int64_t R, int nb, const float* bz, const float* ystats,
                       int64_t row_offset, const float* feat, int64_t ldf, int col, float* logp_acc, float log_eps,
                       hipStream_t s) {
-  if (R <= 0) return;
-  hipLaunchKernelGGL(k_group_nll, dim3((unsigned)R), dim3(256), 64 + (size_t)nb * 4, s, p_rows, per, nb, bz, ystats,
-                     row_offset, feat, ldf, col, logp_acc, log_eps);
+  NPFN_GROUP_LAUNCH(k_group_nll, p_rows, per, nb, bz, ystats, row_offset, feat, ldf, col, logp_acc, log_eps);
 }
 void launch_mix_nll(const logit_t* logits, int64_t R, int E, int nb, float invT, const MixTrans& tr, const float* bz,
                     const float* ystats, int64_t row_offset, const float* feat, int64_t ldf, int col,
@@ -3899,9 +3886,8 @@ void launch_mix_nll(const logit_t* logits, int64_t R, int E, int nb, float invT,
 void launch_group_score(const float* p_rows, int64_t per, int64_t R, int nb, const float* bz, const float* ystats,
                         int64_t row_offset, const float* feat, int64_t ldf, int col, float* logp_out, float* cdf_out,
                         int64_t ldo, float log_eps, hipStream_t s) {
-  if (R <= 0) return;
-  hipLaunchKernelGGL(k_group_score, dim3((unsigned)R), dim3(256), 64 + (size_t)nb * 4, s, p_rows, per, nb, bz, ystats,
-                     row_offset, feat, ldf, col, logp_out, cdf_out, ldo, log_eps);
+  NPFN_GROUP_LAUNCH(k_group_score, p_rows, per, nb, bz, ystats, row_offset, feat, ldf, col, logp_out, cdf_out, ldo,
+                    log_eps);
 }
 void launch_mix_score(const logit_t* logits, int64_t R, int E, int nb, float invT, const MixTrans& tr, const float* bz,
                       const float* ystats, int64_t row_offset, const float* feat, int64_t ldf, int col,

@@ -491,6 +491,26 @@ class Engine:
         return self._stats_dict(m, md, qo)
 
     # -------------------------------------------------------------- fused paths
+    def _ar_ctx(self, who: str, x_ctx, theta_ctx, matched: bool = True):
+        """``(x_ctx, theta_ctx, n, dim_x, dim_theta)`` of an AR call, the tables on the device;
+        ``matched``: they must be matrices of equal row counts."""
+        x_ctx = _dev_f32(x_ctx, self.device)
+        theta_ctx = _dev_f32(theta_ctx, self.device)
+        if matched and (x_ctx.ndim != 2 or theta_ctx.ndim != 2 or theta_ctx.shape[0] != x_ctx.shape[0]):
+            raise ValueError(f"{who}: x_ctx {tuple(x_ctx.shape)} and theta_ctx {tuple(theta_ctx.shape)} do not match")
+        n, dx = x_ctx.shape
+        return x_ctx, theta_ctx, n, dx, theta_ctx.shape[1]
+
+    def _ar_unique(self, who: str, x_unique, N: int, dx: int, one_each: bool = False, of: bool = True):
+        """``(x_unique, U)``: the U distinct query rows, on the device, that repeat into N rows of
+        dx columns; ``one_each``: N >= U as well."""
+        x_unique = _dev_f32(x_unique, self.device)
+        U = x_unique.shape[0] if x_unique.ndim == 2 else 0
+        if x_unique.ndim != 2 or x_unique.shape[1] != dx or U < 1 or (one_each and N < U) or N % U:
+            raise ValueError(f"{who}: x_unique {tuple(x_unique.shape)} does not repeat into {N} rows"
+                             + (f" of {dx}" if of else ""))
+        return x_unique, U
+
     def ar_sample(self, x_ctx, theta_ctx, x_query, counter: int, with_log_prob: bool = False,
                   eps: float = 1e-15, row_base: int = 0,
                   x_unique: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
@@ -498,10 +518,7 @@ class Engine:
         ``x_unique.repeat_interleave(N // U, 0)`` (one observation repeated, or sample_batched's
         obs-major batch): npfn_ar_sample_repeated runs AR step 0 once per distinct row."""
         self.full_range()
-        x_ctx = _dev_f32(x_ctx, self.device)
-        theta_ctx = _dev_f32(theta_ctx, self.device)
-        n, dx = x_ctx.shape
-        dth = theta_ctx.shape[1]
+        x_ctx, theta_ctx, n, dx, dth = self._ar_ctx("ar_sample", x_ctx, theta_ctx, matched=False)
         N = x_query.shape[0]
         if theta_ctx.shape[0] != n or x_query.shape[1] != dx:
             raise ValueError("ar_sample: inconsistent shapes")
@@ -509,10 +526,7 @@ class Engine:
         theta = torch.empty((N, dth), dtype=torch.float32, device=self.device)
         lp = torch.empty(N, dtype=torch.float32, device=self.device) if with_log_prob else None
         if x_unique is not None and not _NO_REPEATED:
-            x_unique = _dev_f32(x_unique, self.device)
-            U = x_unique.shape[0]
-            if x_unique.ndim != 2 or x_unique.shape[1] != dx or U < 1 or N % U:
-                raise ValueError(f"ar_sample: x_unique {tuple(x_unique.shape)} does not repeat into {N} rows of {dx}")
+            x_unique, U = self._ar_unique("ar_sample", x_unique, N, dx)
             _check(self.lib, self.lib.npfn_ar_sample_repeated(
                 self.h, _ptr(x_ctx), _ptr(theta_ctx), n, dx, dth, _ptr(x_unique), U, N, int(counter), int(row_base),
                 _ptr(theta), _ptr(lp), float(eps), self.stream), "npfn_ar_sample_repeated")
@@ -535,18 +549,9 @@ class Engine:
         ``probs[u, k]`` are the bar masses of the marginal of theta_k given ``x_unique[u]`` on
         ``borders[k]``: the mean over the observation's draws of their conditionals."""
         self.full_range()
-        x_ctx = _dev_f32(x_ctx, self.device)
-        theta_ctx = _dev_f32(theta_ctx, self.device)
-        x_unique = _dev_f32(x_unique, self.device)
-        if x_ctx.ndim != 2 or theta_ctx.ndim != 2 or theta_ctx.shape[0] != x_ctx.shape[0]:
-            raise ValueError(f"ar_marginals: x_ctx {tuple(x_ctx.shape)} and theta_ctx {tuple(theta_ctx.shape)} do "
-                             "not match")
-        n, dx = x_ctx.shape
-        dth = theta_ctx.shape[1]
+        x_ctx, theta_ctx, n, dx, dth = self._ar_ctx("ar_marginals", x_ctx, theta_ctx)
         N = int(n_rows)
-        U = x_unique.shape[0] if x_unique.ndim == 2 else 0
-        if x_unique.ndim != 2 or x_unique.shape[1] != dx or U < 1 or N < U or N % U:
-            raise ValueError(f"ar_marginals: x_unique {tuple(x_unique.shape)} does not repeat into {N} rows of {dx}")
+        x_unique, U = self._ar_unique("ar_marginals", x_unique, N, dx, one_each=True)
         self.check_table(n, dx + dth - 1)
         nb = self.cfg.n_bars
         theta = torch.empty((N, dth), dtype=torch.float32, device=self.device)
@@ -570,20 +575,10 @@ class Engine:
         c]``, j < k, is the mass of (theta_j in cell a, theta_k in cell c) given ``x_unique[u]``;
         ``cell[u, k, c]`` the mass of theta_k in cell c."""
         self.full_range()
-        x_ctx = _dev_f32(x_ctx, self.device)
-        theta_ctx = _dev_f32(theta_ctx, self.device)
-        x_unique = _dev_f32(x_unique, self.device)
-        edges = _dev_f32(edges, self.device)
-        if x_ctx.ndim != 2 or theta_ctx.ndim != 2 or theta_ctx.shape[0] != x_ctx.shape[0]:
-            raise ValueError(f"ar_pair_marginals: x_ctx {tuple(x_ctx.shape)} and theta_ctx {tuple(theta_ctx.shape)} "
-                             "do not match")
-        n, dx = x_ctx.shape
-        dth = theta_ctx.shape[1]
+        x_ctx, theta_ctx, n, dx, dth = self._ar_ctx("ar_pair_marginals", x_ctx, theta_ctx)
         N = int(n_rows)
-        U = x_unique.shape[0] if x_unique.ndim == 2 else 0
-        if x_unique.ndim != 2 or x_unique.shape[1] != dx or U < 1 or N < U or N % U:
-            raise ValueError(f"ar_pair_marginals: x_unique {tuple(x_unique.shape)} does not repeat into {N} rows of "
-                             f"{dx}")
+        x_unique, U = self._ar_unique("ar_pair_marginals", x_unique, N, dx, one_each=True)
+        edges = _dev_f32(edges, self.device)
         if edges.ndim != 2 or edges.shape[0] != dth or not bool((edges[:, 1:] > edges[:, :-1]).all()):
             raise ValueError(f"ar_pair_marginals: edges {tuple(edges.shape)} must be [{dth}, G + 1] with strictly "
                              "increasing rows")
@@ -604,21 +599,15 @@ class Engine:
                     x_unique: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``x_unique``: the distinct rows ``x_query`` repeats (as in :meth:`ar_sample`)."""
         self.full_range()
-        x_ctx = _dev_f32(x_ctx, self.device)
-        theta_ctx = _dev_f32(theta_ctx, self.device)
+        x_ctx, theta_ctx, n, dx, dth = self._ar_ctx("ar_log_prob", x_ctx, theta_ctx, matched=False)
         theta = _dev_f32(theta, self.device)
-        n, dx = x_ctx.shape
-        dth = theta_ctx.shape[1]
         N = x_query.shape[0]
         if theta.shape != (N, dth):
             raise ValueError("ar_log_prob: theta shape mismatch")
         self.check_table(n, dx + dth - 1)
         out = torch.empty(N, dtype=torch.float32, device=self.device)
         if x_unique is not None and not _NO_REPEATED:
-            x_unique = _dev_f32(x_unique, self.device)
-            U = x_unique.shape[0]
-            if x_unique.ndim != 2 or x_unique.shape[1] != dx or U < 1 or N % U:
-                raise ValueError(f"ar_log_prob: x_unique {tuple(x_unique.shape)} does not repeat into {N} rows")
+            x_unique, U = self._ar_unique("ar_log_prob", x_unique, N, dx, of=False)
             _check(self.lib, self.lib.npfn_ar_log_prob_repeated(
                 self.h, _ptr(x_ctx), _ptr(theta_ctx), n, dx, dth, _ptr(x_unique), U, _ptr(theta), N, _ptr(out),
                 float(eps), self.stream), "npfn_ar_log_prob_repeated")
@@ -642,20 +631,12 @@ class Engine:
         if not (want_logp or want_cdf):
             raise ValueError("ar_score: nothing asked for (want_logp and want_cdf are both False)")
         self.full_range()
-        x_ctx = _dev_f32(x_ctx, self.device)
-        theta_ctx = _dev_f32(theta_ctx, self.device)
-        x_unique = _dev_f32(x_unique, self.device)
+        x_ctx, theta_ctx, n, dx, dth = self._ar_ctx("ar_score", x_ctx, theta_ctx)
         theta = _dev_f32(theta, self.device)
-        if x_ctx.ndim != 2 or theta_ctx.ndim != 2 or theta_ctx.shape[0] != x_ctx.shape[0]:
-            raise ValueError(f"ar_score: x_ctx {tuple(x_ctx.shape)} and theta_ctx {tuple(theta_ctx.shape)} do not match")
-        n, dx = x_ctx.shape
-        dth = theta_ctx.shape[1]
         if theta.ndim != 2 or theta.shape[1] != dth:
             raise ValueError(f"ar_score: theta {tuple(theta.shape)} is not [N, {dth}]")
         N = theta.shape[0]
-        U = x_unique.shape[0] if x_unique.ndim == 2 else 0
-        if x_unique.ndim != 2 or x_unique.shape[1] != dx or U < 1 or N % U:
-            raise ValueError(f"ar_score: x_unique {tuple(x_unique.shape)} does not repeat into {N} rows of {dx}")
+        x_unique, U = self._ar_unique("ar_score", x_unique, N, dx)
         self.check_table(n, dx + dth - 1)
         lp = torch.empty((N, dth), dtype=torch.float32, device=self.device) if want_logp else None
         cdf = torch.empty((N, dth), dtype=torch.float32, device=self.device) if want_cdf else None

@@ -25,8 +25,9 @@ EDITS = {
     # the row kernel without its feature attention (the v / k / q products and barriers stay)
     "nofa": [("npfn_rowk2.hip", "  feat_attn_rows<LONG>(smem, C, nrows);\n", "")],
     # the fused mix + sample without its sampling tail (block scan, walk, thread 0's inverse CDF / NLL)
-    "mixnotail": [("npfn_kernels.hip", "  bar_sample_row(p, bz, ystats[1], ystats[0], nb, u, red, scan, th, lp);\n  if (threadIdx.x == 0) {\n    feat[(row_offset + r) * ldf + col] = th;",
-                   "  th = u;\n  if (threadIdx.x == 0) {\n    feat[(row_offset + r) * ldf + col] = th;")],
+    # (step_sample: the one tail of k_mix_sample and k_group_sample)
+    "mixnotail": [("npfn_kernels.hip", "  bar_sample_row(p, bz, ystats[1], ystats[0], nb, u, red, scan, th, lp);\n  if (threadIdx.x == 0) {\n    feat[row * ldf + col] = th;",
+                   "  th = u;\n  if (threadIdx.x == 0) {\n    feat[row * ldf + col] = th;")],
     # the fast mix treating every estimator as untranslated (no border translation)
     "mixnotrans": [("npfn_kernels.hip", "    const bool trans = tr.ett != nullptr && tr.ett[e];\n    f32x4 v[NV];",
                     "    const bool trans = false;\n    f32x4 v[NV];")],
