@@ -522,6 +522,46 @@ int npfn_mmd_sums(const float* z, int64_t n_obs, int64_t n_pool, int32_t dim, in
                   const float* bandwidths, int32_t n_bw, const uint8_t* labels, int32_t n_label,
                   int64_t* sums, int64_t* total, int32_t* bad, void* stream);
 
+/* Exact 2-Wasserstein assignment (npe_pfn.diagnostics.wasserstein_batched; the reference's
+ * sqrt(ot.emd2(uniform, uniform, ot.dist(a, b))), scripts/evaluate_ropefm.py:592-710; needs no
+ * engine).  a, b [n_obs, n, dim] (device): per observation two sets of n points with weight 1 / n
+ * each, for which optimal transport under the squared-Euclidean cost is a linear assignment
+ * problem.  scale [n_obs] double (device): the caller's power of two per observation
+ * (npe_pfn.diagnostics.transport_scale) with d2 * scale <= 2^41.  Outputs (device), ZEROED BY THE
+ * CALL itself on `stream`: assign [n_obs, n] int32, duals [n_obs, 2, n] int64 (may be NULL),
+ * cost_sum [n_obs] int64, steps [n_obs] int64 (may be NULL), bad [n_obs] int32.
+ *  - d2(i, j), fp32, as in npfn_mmd_sums: acc = 0; for k ascending t = fl(a_i[k] - b_j[k]), acc =
+ *    fl(acc + fl(t * t)), every operation rounded on its own;
+ *  - cq(i, j) = llrint((double)d2 * scale) (round half to even), an integer in 0..2^41;
+ *  - the shortest-augmenting-path Hungarian method from zero duals, all in int64: rows i = 0..n-1
+ *    are inserted in order; for row i, minv[j] = INF, used[j] = false and a virtual column holds
+ *    row i; a step marks the current column j0 used, takes its row i0, sets for every unused j cur
+ *    = cq[i0][j] - u[i0] - v[j] and, where cur < minv[j] (strictly), minv[j] = cur, way[j] = j0;
+ *    delta = the minimum of minv over the unused columns, j1 its LOWEST column; u[row of j] +=
+ *    delta and v[j] -= delta over the used columns (the virtual one's row i included), minv[j] -=
+ *    delta over the unused; j0 = j1, until j0 has no row; then the path is flipped along way;
+ *  - assign[u][i] = the column of b matched to row i of a, duals[u][0] = u, duals[u][1] = v,
+ *    cost_sum[u] = sum over i of cq(i, assign[i]) (= sum(u) + sum(v)), steps[u] = the number of
+ *    steps, at most n (n + 1) / 2.
+ * All four equal npe_pfn.diagnostics.assignment_solve_host on transport_costs_host's cq bit for
+ * bit, whatever the other observations of the call.  With n <= 2048 every potential and sum stays
+ * below 2^53.  bad[u] = 1 for a non-finite coordinate, 2 for a cost above 2^41 (the scale broke
+ * its promise), 3 for a step counter past n (n + 1) / 2; the observation's other outputs are then
+ * unspecified.
+ * Kernel: one workgroup per observation, of the smallest power of two of threads in 64..1024 that
+ * is >= n / 2; a thread owns columns j and j + blockDim with their v, minv, way and used flag in
+ * registers; u and the column -> row map are in LDS, as is b transposed (and a when both fit in
+ * 159 KiB; otherwise the one row of a is read from global memory); each step recomputes its cost
+ * row, reduces (value, lowest index) with DPP / permlane inside the wave and one LDS hop across
+ * waves, and has one barrier.  No n x n array reaches global memory; no workgroup waits on
+ * another.  Asynchronous; n_obs == 0 launches nothing.
+ * Errors (host, before any launch): NPFN_EINVAL (message starting "w2_assign") for n_obs < 0, n
+ * outside 1..2048, dim outside 1..64, n * dim > 32768 (b's LDS image), or a missing a, b, scale,
+ * assign, cost_sum or bad. */
+int npfn_w2_assign(const float* a, const float* b, int64_t n_obs, int32_t n, int32_t dim,
+                   const double* scale, int32_t* assign, int64_t* duals, int64_t* cost_sum,
+                   int64_t* steps, int32_t* bad, void* stream);
+
 /* K12 standardized-Euclidean context filter (support_posterior.py:357-369):
  * idx_out[0:k] = indices of the k rows of x [n_rows, dim] closest to obs in
  * z-scored Euclidean distance, ascending (ties by lower index). */

@@ -129,6 +129,46 @@ __device__ __forceinline__ float wave_incl_scan_dpp(float v) {
   return v;
 }
 
+// (v, j) <- the smaller of (v, j) and (ov, oj): by value, then by index
+__device__ __forceinline__ void argmin_take(long long& v, int& j, long long ov, int oj) {
+  const bool t = ov < v || (ov == v && oj < j);
+  v = t ? ov : v;
+  j = t ? oj : j;
+}
+template <int CTRL>
+__device__ __forceinline__ void argmin_dpp(long long& v, int& j) {
+  const int lo = __builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, 0xF, 0xF, false);
+  const int hi = __builtin_amdgcn_update_dpp((int)(v >> 32), (int)(v >> 32), CTRL, 0xF, 0xF, false);
+  const int oj = __builtin_amdgcn_update_dpp(j, j, CTRL, 0xF, 0xF, false);
+  argmin_take(v, j, (long long)(((unsigned long long)(uint32_t)hi << 32) | (uint32_t)lo), oj);
+}
+// Wave-wide minimum of a 64-bit integer with the lowest index among equal values, on the lanes of
+// wave_max_dpp (all 64 lanes active; every lane gets the result).  The order (value, index) is
+// total when the indices differ, so the result does not depend on the order of the combines; a
+// permlane swap hands a lane {own, partner} in one order for all three words.
+__device__ __forceinline__ void wave_argmin_i64(long long& v, int& j) {
+  argmin_dpp<0xB1>(v, j);
+  argmin_dpp<0x4E>(v, j);
+  argmin_dpp<0x141>(v, j);
+  argmin_dpp<0x140>(v, j);
+  {
+    const auto lo = __builtin_amdgcn_permlane16_swap((uint32_t)v, (uint32_t)v, false, false);
+    const auto hi = __builtin_amdgcn_permlane16_swap((uint32_t)(v >> 32), (uint32_t)(v >> 32), false, false);
+    const auto jj = __builtin_amdgcn_permlane16_swap((uint32_t)j, (uint32_t)j, false, false);
+    v = (long long)(((unsigned long long)hi[0] << 32) | lo[0]);
+    j = (int)jj[0];
+    argmin_take(v, j, (long long)(((unsigned long long)hi[1] << 32) | lo[1]), (int)jj[1]);
+  }
+  {
+    const auto lo = __builtin_amdgcn_permlane32_swap((uint32_t)v, (uint32_t)v, false, false);
+    const auto hi = __builtin_amdgcn_permlane32_swap((uint32_t)(v >> 32), (uint32_t)(v >> 32), false, false);
+    const auto jj = __builtin_amdgcn_permlane32_swap((uint32_t)j, (uint32_t)j, false, false);
+    v = (long long)(((unsigned long long)hi[0] << 32) | lo[0]);
+    j = (int)jj[0];
+    argmin_take(v, j, (long long)(((unsigned long long)hi[1] << 32) | lo[1]), (int)jj[1]);
+  }
+}
+
 __device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -7,9 +7,9 @@ this directory (``npe-pfn_amd``) on ``sys.path``.  The TabPFN forward runs in
 the HIP engine ``npe_pfn/_lib/libnpfn.so`` (C-ABI: include/npfn.h).
 """
 
-from npe_pfn.diagnostics import (CoverageRanks, TwoSampleResult, bar_cdf, expected_coverage, mmd_batched,
-                                 mmd_sums_host, permutation_labels, pit_ks_statistic, rank_accumulate_host,
-                                 rank_ks_statistic)
+from npe_pfn.diagnostics import (CoverageRanks, TransportResult, TwoSampleResult, assignment_solve_host, bar_cdf,
+                                 expected_coverage, mmd_batched, mmd_sums_host, permutation_labels, pit_ks_statistic,
+                                 rank_accumulate_host, rank_ks_statistic, transport_costs_host, wasserstein_batched)
 from npe_pfn.marginals import PosteriorMarginals
 from npe_pfn.npe_pfn import NPE_PFN_Core, TabPFN_Based_NPE_PFN, TabPFN_Based_Uncond_Estimator
 from npe_pfn.pair_marginals import PosteriorPairMarginals
@@ -24,7 +24,9 @@ __all__ = [
     "PosteriorPairMarginals",
     "TabPFN_Based_NPE_PFN",
     "TabPFN_Based_Uncond_Estimator",
+    "TransportResult",
     "TwoSampleResult",
+    "assignment_solve_host",
     "bar_cdf",
     "expected_coverage",
     "mmd_batched",
@@ -34,4 +36,6 @@ __all__ = [
     "rank_accumulate_host",
     "rank_ks_statistic",
     "run_tsnpe_pfn",
+    "transport_costs_host",
+    "wasserstein_batched",
 ]

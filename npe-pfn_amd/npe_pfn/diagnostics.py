@@ -16,6 +16,11 @@ curve.
 Distance between two sets of draws (``mmd_batched``, ``NPE_PFN_Core.mmd_batched``): the reference
 harness's MMD with a permutation null.  ``mmd_sums_host`` is the definition of the engine's
 ``npfn_mmd_sums``, ``permutation_labels`` the relabellings, ``TwoSampleResult`` what comes back.
+
+Exact 2-Wasserstein distance between two equally sized sets of draws (``wasserstein_batched``,
+``NPE_PFN_Core.wasserstein_batched``): the reference harness's ``sqrt(ot.emd2(...))`` as a linear
+assignment problem on integer costs.  ``transport_costs_host`` and ``assignment_solve_host`` are
+the definition of the engine's ``npfn_w2_assign``, ``TransportResult`` what comes back.
 """
 
 from __future__ import annotations
@@ -24,10 +29,11 @@ import math
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 from torch import Tensor
 
-from .engine import MMD_MAX_LABELLINGS, check_mmd_args
+from .engine import MMD_MAX_LABELLINGS, check_mmd_args, check_transport_args
 
 HALFNORMAL_MEDIAN = 0.6744897501960817  # median of |N(0, 1)|: the tail bars' scale is width / this
 
@@ -420,3 +426,201 @@ def mmd_batched(a, b, kernel: str = "rbf", bandwidths=None, num_permutations: in
     biased, null = stat[:, 0].contiguous(), stat[:, 1:].contiguous()
     return TwoSampleResult(biased, unbiased, null, mmd_p_value(biased, null) if P > 0 else None, n, m, kernel,
                            tuple(bw))
+
+
+# ------------------------------------------------------------------ exact 2-Wasserstein distance
+W2_MAX_COST = 2 ** 41   # npfn_w2_assign's bound on an integer cost
+
+
+def transport_scale(a: Tensor, b: Tensor) -> Tuple[Tensor, Tensor]:
+    """``(scale [M] float64, nonfinite [M] bool)`` of ``a`` and ``b`` [M, n, d] fp32, on their
+    device, without a host synchronisation.  Per observation, from its own pooled points only and
+    in fp64: bound = (1 + 2^-10) * sum over k of (max_k - min_k)^2 (above every fp32 d2 of the
+    observation: the chain's rounding is below d 2^-24), scale = 2^floor(log2(2^40 / bound)), an
+    exact power of two, 1 for bound = 0 or a non-finite coordinate."""
+    z = torch.cat([a, b], 1).to(torch.float64)
+    nonfinite = ~torch.isfinite(z).all(2).all(1)
+    rng = z.max(1).values - z.min(1).values
+    bound = (1.0 + 2.0 ** -10) * (rng * rng).sum(1)
+    ok = (bound > 0) & torch.isfinite(bound) & ~nonfinite
+    _, ex = torch.frexp(2.0 ** 40 / torch.where(ok, bound, torch.ones_like(bound)))   # quotient in [2^(ex-1), 2^ex)
+    e = torch.where(ok, (ex - 1).clamp(-1000, 1000), torch.zeros_like(ex))
+    return torch.ldexp(torch.ones_like(bound), e), nonfinite
+
+
+def transport_costs_host(a, b) -> Tuple[Tensor, Tensor, Tensor]:
+    """``(cq [M, n, n] int64, scale [M] float64, bad [M] int32)`` -- the integer costs that the
+    engine's ``npfn_w2_assign`` recomputes row by row, in torch on the device of ``a``.
+
+    ``a`` and ``b`` are [M, n, d] fp32.  d2(i, j) is ``npfn_mmd_sums``' chain: in fp32, k ascending,
+    t = a_i[k] - b_j[k], acc = acc + t * t, every operation rounded on its own.  ``scale`` is
+    :func:`transport_scale`'s power of two, and cq(i, j) = round(d2 * scale) in fp64 (exact product,
+    round half to even), so 0 <= cq <= 2^41; with n <= 2048 every potential and sum of the solver
+    stays below 2^53.  An observation with a non-finite coordinate gets bad = 1, one with a cost
+    above 2^41 (a d2 that overflowed fp32) bad = 2; both get zero costs."""
+    a = torch.as_tensor(a).detach().to(torch.float32)
+    b = torch.as_tensor(b).detach().to(device=a.device, dtype=torch.float32)
+    M, n, d = check_transport_args(a.shape, b.shape)
+    scale, nonfinite = transport_scale(a, b)
+    d2 = torch.zeros((M, n, n), dtype=torch.float32, device=a.device)
+    for k in range(d):   # ascending, one rounding per operation: the kernel's own chain
+        t = a[:, :, None, k] - b[:, None, :, k]
+        d2 = d2 + t * t
+    p = d2.to(torch.float64) * scale[:, None, None]
+    over = ~(p <= float(W2_MAX_COST)).all(2).all(1) & ~nonfinite
+    drop = nonfinite | over
+    cq = torch.round(torch.where(drop[:, None, None], torch.zeros_like(p), p)).to(torch.int64)
+    bad = nonfinite.to(torch.int32) + 2 * over.to(torch.int32)
+    return cq, scale, bad
+
+
+def _assignment_solve_one(c: "np.ndarray"):
+    n = c.shape[0]
+    inf = np.iinfo(np.int64).max
+    u, v = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+    row = np.full(n, -1, dtype=np.int64)   # column -> row
+    way = np.empty(n, dtype=np.int64)
+    steps = 0
+    for i in range(n):
+        minv = np.full(n, inf, dtype=np.int64)
+        used = np.zeros(n, dtype=bool)
+        way[:] = -1                        # -1: the virtual column, which holds row i
+        j0, i0 = -1, i
+        while True:
+            steps += 1
+            if j0 >= 0:
+                used[j0] = True
+            free = ~used
+            cur = c[i0] - u[i0] - v
+            better = free & (cur < minv)
+            minv[better] = cur[better]
+            way[better] = j0
+            masked = np.where(free, minv, inf)
+            j1 = int(np.argmin(masked))    # the lowest column of the minimum
+            delta = masked[j1]
+            u[row[used]] += delta
+            u[i] += delta
+            v[used] -= delta
+            minv[free] -= delta
+            j0, i0 = j1, int(row[j1])
+            if i0 < 0:
+                break
+        while j0 >= 0:
+            j1 = int(way[j0])
+            row[j0] = i if j1 < 0 else row[j1]
+            j0 = j1
+    assign = np.empty(n, dtype=np.int64)
+    assign[row] = np.arange(n)
+    return assign, u, v, int(c[np.arange(n), assign].sum()), steps
+
+
+def assignment_solve_host(cq) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """``(assign [M, n] int32, duals [M, 2, n] int64, cost_sum [M] int64, steps [M] int64)`` (CPU)
+    of the linear assignment problems ``cq`` [M, n, n] int64 -- the definition of the engine's
+    ``npfn_w2_assign``: the shortest-augmenting-path Hungarian method from zero duals, in int64.
+
+    Rows i = 0..n-1 are inserted in order.  For row i: minv[j] = INF, used[j] = false, and a
+    virtual column holds row i.  A step marks the current column j0 used and takes its row i0; for
+    every unused column j, cur = cq[i0][j] - u[i0] - v[j], and where cur < minv[j] (strictly)
+    minv[j] = cur and way[j] = j0; delta is the minimum of minv over the unused columns and j1 its
+    lowest column; u[row of j] += delta and v[j] -= delta over the used columns (the virtual one,
+    i.e. u[i], included), minv[j] -= delta over the unused ones; j0 = j1, and the steps end when
+    j0 has no row.  Then the path is flipped along way.  ``steps`` counts the steps (at most n (n +
+    1) / 2), ``assign[i]`` is the column matched to row i, ``duals`` is (u, v): u_i + v_j <= cq_ij
+    everywhere with equality on the assignment, so cost_sum = sum_i cq[i, assign[i]] = sum(u) +
+    sum(v) certifies optimality.  Vectorised over the columns in numpy: n = 1000 takes seconds."""
+    c = torch.as_tensor(cq).detach().cpu().to(torch.int64).numpy()
+    if c.ndim != 3 or c.shape[1] != c.shape[2] or c.shape[1] < 1:
+        raise ValueError(f"assignment_solve_host: cq {c.shape} is not [M, n >= 1, n]")
+    M, n, _ = c.shape
+    assign = torch.zeros((M, n), dtype=torch.int32)
+    duals = torch.zeros((M, 2, n), dtype=torch.int64)
+    cost_sum, steps = torch.zeros(M, dtype=torch.int64), torch.zeros(M, dtype=torch.int64)
+    for m in range(M):
+        asg, u, v, total, st = _assignment_solve_one(c[m])
+        assign[m] = torch.from_numpy(asg).to(torch.int32)
+        duals[m, 0], duals[m, 1] = torch.from_numpy(u), torch.from_numpy(v)
+        cost_sum[m], steps[m] = total, st
+    return assign, duals, cost_sum, steps
+
+
+@dataclass
+class TransportResult:
+    """Exact 2-Wasserstein distance between two sets of n draws per observation
+    (:func:`wasserstein_batched`), on the device of the draws.  ``wasserstein`` [M] float64 is the
+    reference's number sqrt(sum_i d2(i, assignment[i]) / n) = sqrt(cost_sum / scale / n) and
+    ``w2_squared`` [M] its square; ``assignment`` [M, n] int64 is the optimal matching (row i of a
+    with row assignment[i] of b); ``cost_sum`` [M] int64 its total integer cost at ``scale`` [M]
+    float64, a power of two; ``steps`` [M] int64 the solver's steps (-1 where another solver ran).
+    An observation with a non-finite draw is NaN, its assignment -1."""
+
+    wasserstein: Tensor
+    w2_squared: Tensor
+    assignment: Tensor
+    cost_sum: Tensor
+    scale: Tensor
+    steps: Tensor
+    n: int
+
+
+def wasserstein_batched(a, b, z_score: bool = False, engine=None) -> TransportResult:
+    """Exact 2-Wasserstein distance between ``a`` and ``b`` [M, n, d], observation by observation
+    (2-D inputs: M = 1): the reference's ``sqrt(ot.emd2(uniform, uniform, ot.dist(a, b)))``
+    (scripts/evaluate_ropefm.py:592-710).  Between two uniform sets of equal size optimal transport
+    is a linear assignment problem; it is solved exactly on the integer costs round(d2 * scale),
+    scale a power of two per observation (:func:`transport_scale`), so the only error against the
+    real-valued problem is d2's fp32 rounding and 2^-41 of the largest cost.  n <= 2048, d <= 64,
+    n * d <= 32768.  ``z_score=True`` standardises both sets by ``a``'s per-observation mean and
+    unbiased std first (a zero std counts as 1), as in :func:`mmd_batched`.
+
+    Tensors on the GPU go through ``npfn_w2_assign`` (``engine.w2_assign`` when an engine is given,
+    otherwise the library's engine-free entry), one workgroup per observation, and equal
+    :func:`assignment_solve_host` on :func:`transport_costs_host` bit for bit.  CPU tensors go
+    through :func:`transport_costs_host` and ``scipy.optimize.linear_sum_assignment``: the same
+    ``cost_sum``, a valid optimal assignment (not necessarily the same one), ``steps`` = -1."""
+    a, b = torch.as_tensor(a).detach(), torch.as_tensor(b).detach()
+    if a.ndim == 2 and b.ndim == 2:
+        a, b = a[None], b[None]
+    if a.ndim != 3 or b.ndim != 3 or a.shape[0] != b.shape[0] or a.shape[2] != b.shape[2] or a.shape[1] < 1 \
+            or b.shape[1] < 1:
+        raise ValueError(f"wasserstein_batched: a {tuple(a.shape)} and b {tuple(b.shape)} are not both [M, n >= 1, d] "
+                         "(or [n, d])")
+    if a.shape[1] != b.shape[1]:
+        raise ValueError(f"wasserstein_batched: a has {a.shape[1]} points and b {b.shape[1]}: uniform transport "
+                         "between sets of unequal size is not an assignment (an optimal plan splits mass), and the "
+                         "reference harness always compares sets of equal size")
+    M, n, _ = check_transport_args(a.shape, b.shape)
+    if z_score and n < 2:
+        raise ValueError("wasserstein_batched: z_score needs n >= 2 draws in a (the unbiased std)")
+    dev = a.device
+    a, b = a.to(torch.float32), b.to(device=dev, dtype=torch.float32)
+    if z_score:
+        mu, sd = a.mean(1, keepdim=True), a.std(1, keepdim=True)
+        sd = torch.where(sd == 0, torch.ones_like(sd), sd)
+        a, b = (a - mu) / sd, (b - mu) / sd
+    if dev.type == "cuda":
+        from .engine import w2_assign
+
+        scale, _ = transport_scale(a, b)
+        assign, _, cost_sum, steps, bad = engine.w2_assign(a, b, scale) if engine is not None else \
+            w2_assign(a, b, scale)
+        assign, cost_sum, steps, bad = assign.to(dev).to(torch.int64), cost_sum.to(dev), steps.to(dev), bad.to(dev)
+        scale = scale.to(dev)
+    else:
+        from scipy.optimize import linear_sum_assignment
+
+        cq, scale, bad = transport_costs_host(a, b)
+        assign = torch.zeros((M, n), dtype=torch.int64)
+        cost_sum = torch.zeros(M, dtype=torch.int64)
+        steps = torch.full((M,), -1, dtype=torch.int64)
+        for m in range(M):
+            if int(bad[m]) == 0:
+                c = cq[m].numpy()
+                rows, cols = linear_sum_assignment(c)
+                assign[m, torch.from_numpy(rows)] = torch.from_numpy(cols)
+                cost_sum[m] = int(c[rows, cols].sum())
+    nan = bad != 0
+    w2 = cost_sum.to(torch.float64) / (scale * float(n))   # scale * n is exact: one rounding
+    w2 = torch.where(nan, torch.full_like(w2, float("nan")), w2)
+    assign = torch.where(nan[:, None], torch.full_like(assign, -1), assign)
+    return TransportResult(torch.sqrt(w2), w2, assign, cost_sum, scale, steps, n)

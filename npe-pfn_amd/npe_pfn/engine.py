@@ -112,6 +112,8 @@ SIGNATURES = {
                                             ctypes.POINTER(_i32), _vp]),
     "npfn_mmd_sums": (ctypes.c_int, [_vp, _i64, _i64, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp,
                                      ctypes.POINTER(_i32), _vp]),
+    "npfn_w2_assign": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, ctypes.POINTER(_i32), _vp, _vp, _vp,
+                                      ctypes.POINTER(_i32), _vp]),
     "npfn_filter_stdeuclid": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i64, _vp, _vp]),
     "npfn_sir_select": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _u64, _u64, _i64, _vp, _i32, _vp, _vp, _vp, _vp]),
     "npfn_kmeans_fit": (ctypes.c_int, [_vp, _i64, _i32, _i32, _u64, _i32, _f, _vp, _vp, _vp, _vp, _vp]),
@@ -243,6 +245,62 @@ def mmd_sums(z, labels, kernel, bandwidths, lib=None) -> Tuple[torch.Tensor, tor
                                       ctypes.cast(ctypes.c_void_p(bad.data_ptr()), ctypes.POINTER(_i32)), stream),
                "npfn_mmd_sums")
     return sums, total, bad
+
+
+W2_MAX_N, W2_MAX_DIM, W2_MAX_IMAGE = 2048, 64, 32768   # npfn_w2_assign's caps (n * dim <= the image)
+
+
+def check_transport_args(a_shape, b_shape) -> Tuple[int, int, int]:
+    """(n_obs, n, dim) of a w2_assign call on ``a`` and ``b`` [n_obs, n, dim]; ValueError for
+    whatever npfn_w2_assign would refuse, and for two sets of unequal size.  Pure host logic,
+    shared by :func:`w2_assign` and :func:`npe_pfn.diagnostics.transport_costs_host`."""
+    a_shape, b_shape = tuple(a_shape), tuple(b_shape)
+    if len(a_shape) != 3 or len(b_shape) != 3 or a_shape[0] != b_shape[0] or a_shape[2] != b_shape[2]:
+        raise ValueError(f"w2_assign: a {a_shape} and b {b_shape} are not both [n_obs, n, dim]")
+    if a_shape[1] != b_shape[1]:
+        raise ValueError(f"w2_assign: a has {a_shape[1]} points and b {b_shape[1]}: uniform transport between sets "
+                         "of unequal size is not an assignment (an optimal plan splits mass), and the reference "
+                         "harness always compares sets of equal size")
+    n_obs, n, dim = a_shape
+    if not 1 <= n <= W2_MAX_N or not 1 <= dim <= W2_MAX_DIM or n * dim > W2_MAX_IMAGE:
+        raise ValueError(f"w2_assign: a {a_shape} is not [n_obs, 1 <= n <= {W2_MAX_N}, 1 <= dim <= {W2_MAX_DIM}] with "
+                         f"n * dim <= {W2_MAX_IMAGE}")
+    return n_obs, n, dim
+
+
+def w2_assign(a, b, scale, lib=None):
+    """npfn_w2_assign on the GPU that holds ``a`` (needs no engine): ``(assign [n_obs, n] int32,
+    duals [n_obs, 2, n] int64, cost_sum [n_obs] int64, steps [n_obs] int64, bad [n_obs] int32)``
+    on that device, on its current stream.  ``a`` and ``b`` [n_obs, n, dim] are the two sets of
+    every observation, ``scale`` [n_obs] float64 its power of two
+    (:func:`npe_pfn.diagnostics.transport_scale`).  The exact assignment under the integer costs
+    round(d2 * scale); the definition of every number:
+    :func:`npe_pfn.diagnostics.transport_costs_host` and
+    :func:`npe_pfn.diagnostics.assignment_solve_host`.  ValueError for arguments that do not fit,
+    before the C call."""
+    a, b = torch.as_tensor(a), torch.as_tensor(b)
+    if a.device.type != "cuda":
+        raise ValueError("w2_assign: a must live on the GPU (npe_pfn.diagnostics.assignment_solve_host is the CPU "
+                         "statement)")
+    n_obs, n, dim = check_transport_args(a.shape, b.shape)
+    scale = torch.as_tensor(scale)
+    if tuple(scale.shape) != (n_obs,):
+        raise ValueError(f"w2_assign: scale {tuple(scale.shape)} is not [{n_obs}]")
+    a = a.to(torch.float32).contiguous()
+    b = b.to(device=a.device, dtype=torch.float32).contiguous()
+    scale = scale.to(device=a.device, dtype=torch.float64).contiguous()
+    assign = torch.empty((n_obs, n), dtype=torch.int32, device=a.device)
+    duals = torch.empty((n_obs, 2, n), dtype=torch.int64, device=a.device)
+    cost_sum = torch.empty((n_obs,), dtype=torch.int64, device=a.device)
+    steps = torch.empty((n_obs,), dtype=torch.int64, device=a.device)
+    bad = torch.empty((n_obs,), dtype=torch.int32, device=a.device)
+    lib = lib or load_library()
+    i32p = lambda t: ctypes.cast(ctypes.c_void_p(t.data_ptr()), ctypes.POINTER(_i32))  # noqa: E731
+    with torch.cuda.device(a.device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)
+        _check(lib, lib.npfn_w2_assign(_ptr(a), _ptr(b), n_obs, n, dim, _ptr(scale), i32p(assign), _ptr(duals),
+                                       _ptr(cost_sum), _ptr(steps), i32p(bad), stream), "npfn_w2_assign")
+    return assign, duals, cost_sum, steps, bad
 
 
 MAX_QUANTILES = 64  # npfn_bar_stats / npfn_predict_stats take at most this many levels per call
@@ -847,6 +905,14 @@ class Engine:
         labels = torch.as_tensor(labels)
         check_mmd_args(z.shape, labels.shape, kernel, bandwidths)
         return mmd_sums(z.to(self.device), labels.to(self.device), kernel, bandwidths, lib=self.lib)
+
+    # ------------------------------------------------- exact W2 assignment (npfn_transport.hip)
+    def w2_assign(self, a, b, scale):
+        """npfn_w2_assign on the engine's device and stream: :func:`w2_assign` of this module (the
+        entry needs no engine; this method moves the arguments to the engine's device)."""
+        a, b = torch.as_tensor(a), torch.as_tensor(b)
+        check_transport_args(a.shape, b.shape)
+        return w2_assign(a.to(self.device), b.to(self.device), torch.as_tensor(scale).to(self.device), lib=self.lib)
 
     def filter_stdeuclid(self, x: torch.Tensor, obs: torch.Tensor, k: int) -> torch.Tensor:
         x = _dev_f32(x, self.device)
