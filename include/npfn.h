@@ -146,7 +146,8 @@ int npfn_predict_proba(npfn_engine* h, const float* Xq, int64_t ldq, int64_t n_r
 int npfn_get_borders(npfn_engine* h, float* borders, void* stream);
 
 /* criterion.sample(logits) (npe_pfn.py:146, 220): inverse-CDF sample of each
- * row with u = Philox4x32-10(counter=(row, counter), key=seed). */
+ * row with u = Philox4x32-10(counter=(row, counter), key=seed).  A row with no finite logit
+ * (no mass) draws NaN, as npfn_bar_stats answers such a row. */
 int npfn_bar_sample(const float* logits, const float* borders, int64_t n_rows, int32_t n_bars,
                     uint64_t seed, uint64_t counter, float* out, void* stream);
 
@@ -729,6 +730,77 @@ int npfn_prof_read(npfn_engine* h, npfn_prof_entry* out, int32_t max_entries, in
  * npfn_kernels.h ViewLayout) to the HOST buffer out (capacity rows * max_cols floats).
  * Synchronous.  Used by the tests to pin the device SVD and SHA-256 fingerprints. */
 int npfn_debug_views(npfn_engine* h, float* out, int64_t rows, int32_t max_cols, int32_t* vw_out);
+
+/* Diagnostics: the target-border translation of the last regressor fit, copied to HOST buffers.
+ * Synchronous.  n_bars / n_est must be the engine's (they size the buffers).  ystats [6]: the
+ * target's mean, std and the fit's third statistic, then (ensemble mode) mean, std and mean
+ * z-score of the Yeo-Johnson-transformed target; *ylam its lambda; idx / share [n_bars + 1]: per
+ * common border the source bucket and the share of it left of the border, share = -1 for a border
+ * at / below the source range and 2 for one at / above it; tcancel [n_bars]: 1 for a bar the
+ * border repair cancelled; ett [n_est]: 1 for an estimator whose bars are translated;
+ * *translated = 1.  When no estimator of the current preprocessing mode transforms its target,
+ * *translated = 0, ett is all 0, ystats[0..2] are written, ystats[3..5] and *ylam are NaN and the
+ * tables are left alone ("no translation").  Used by the tests to feed npfn_mix_rows the engine's
+ * own tables.
+ * Errors: NPFN_EINVAL for a NULL engine or pointer, or n_bars / n_est that are not the engine's;
+ * NPFN_ESTATE before a regressor fit. */
+int npfn_debug_target_translation(npfn_engine* h, int32_t n_bars, int32_t n_est, double* ylam, float* ystats,
+                                  int32_t* idx, float* share, uint8_t* tcancel, int32_t* ett,
+                                  int32_t* translated);
+
+/* Diagnostics: the ensemble mix and its step tails on caller-made logits (needs no engine).  One
+ * 256-thread workgroup per row; the kernels are those of npfn_predict / npfn_ar_sample /
+ * npfn_ar_log_prob / npfn_ar_score, picked by op through the same launchers, so a call on
+ * npfn_forward_logits' output with npfn_debug_target_translation's tables reproduces those calls
+ * bit for bit.  All pointers but the stream are DEVICE pointers.  Asynchronous.
+ *   logits [n_est][ld_rows][n_bars] fp16; rows [row0, row0 + n_rows) are mixed (a window only for
+ *   NPFN_MIX_LOG; the other ops need row0 = 0, ld_rows = n_rows).  Estimator e's row gives q_e =
+ *   softmax(logits * inv_temperature); where ett[e] != 0 the bars with tcancel != 0 are removed
+ *   first and q_e is translated through tab ([n_bars + 1] pairs (int32 idx, float share), the
+ *   layout of npfn_debug_target_translation's idx / share interleaved).  ett / tab / tcancel may
+ *   all be NULL (no translation); tcancel must be readable to n_bars + 4 bytes.  The mixture is
+ *   p = mean_e q_e, or softmax(mean_e log q_e) for geo = 1.  An estimator row with no finite
+ *   logit (after the cancelled bars are removed) has no mass: it adds nothing to the mean (the
+ *   mean still divides by n_est), and under geo, or when every estimator is empty, the row has
+ *   no mass at all.  Both code paths (the register path for n_bars % 4 == 0 up to 8192 bars and
+ *   the generic one) follow this rule.  A row with no mass gives p = 0 (log: -inf), NaN for its
+ *   draw, log density and CDF, as npfn_bar_stats documents.
+ *   NPFN_MIX_LOG   out0[r * ldo + b] = log p_b (ldo >= n_bars).
+ *   NPFN_MIX_PROB  out0[r * n_bars + b] = p_b.
+ *   NPFN_MIX_SAMPLE  row r is global row g = row_offset + r: u = the Philox uniform of (seed,
+ *     counter, philox_row0 + g); feat[g * ldf + col] = the draw (npfn_bar_sample's arithmetic on
+ *     the borders bz * ystats[1] + ystats[0], bz [n_bars + 1]); if out0 != NULL, out0[g] += the
+ *     draw's log density (-inf -> log_eps).
+ *   NPFN_MIX_NLL   out0[g] += log density of feat[g * ldf + col] (npfn_bar_nll; -inf -> log_eps).
+ *   NPFN_MIX_SCORE out0[g * ldo] = that log density, out1[g * ldo] = the CDF there (npfn_bar_cdf);
+ *     either may be NULL.
+ *   NPFN_MIX_GROUP_SAMPLE / _NLL / _SCORE  the same three tails with `logits` holding fp32 masses
+ *     [*, n_bars] (a NPFN_MIX_PROB result): global row g reads row g / per.  n_est,
+ *     inv_temperature, the translation, geo, ld_rows and row0 are ignored.  Equal to their
+ *     NPFN_MIX_* twins bit for bit.
+ * Errors (host, before any launch; message starting "mix_rows"): NPFN_EINVAL for an unknown op;
+ * n_rows < 0 or >= 2^31; n_bars < 2; NULL logits; n_est outside 1..64; inv_temperature not
+ * positive and finite; ett / tab / tcancel partly given; geo outside 0..1; a row window outside
+ * ld_rows, or any window for an op other than NPFN_MIX_LOG; per < 1 (group ops); for the tails a
+ * NULL bz / ystats / feat, row_offset < 0 or col outside [0, ldf); a missing output (out0; for
+ * score both NULL, or ldo < 1; for log ldo < n_bars); or n_bars whose LDS need per workgroup --
+ * 64 + 4 n_bars (+ 8 n_bars with translation; the register path overlays the two) + 2048 B --
+ * exceeds hipDeviceAttributeMaxSharedMemoryPerBlock (such a call is never launched;
+ * npfn_engine_create refuses the same n_bars).  NPFN_EHIP if the runtime refuses the launch.
+ * n_rows = 0 is a no-op. */
+#define NPFN_MIX_LOG 0
+#define NPFN_MIX_PROB 1
+#define NPFN_MIX_SAMPLE 2
+#define NPFN_MIX_NLL 3
+#define NPFN_MIX_SCORE 4
+#define NPFN_MIX_GROUP_SAMPLE 5
+#define NPFN_MIX_GROUP_NLL 6
+#define NPFN_MIX_GROUP_SCORE 7
+int npfn_mix_rows(int32_t op, const void* logits, int64_t ld_rows, int64_t row0, int64_t n_rows, int32_t n_est,
+                  int32_t n_bars, float inv_temperature, const int32_t* ett, const void* tab,
+                  const uint8_t* tcancel, int32_t geo, const float* bz, const float* ystats, uint64_t seed,
+                  uint64_t counter, int64_t row_offset, uint64_t philox_row0, int64_t per, float* feat,
+                  int64_t ldf, int32_t col, float* out0, float* out1, int64_t ldo, float log_eps, void* stream);
 
 /* Diagnostics (process-wide): enable != 0 makes every item-attention block run its
  * online-softmax pass as well (the fallback of the reference-free first pass), so the

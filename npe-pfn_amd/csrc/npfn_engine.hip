@@ -1778,6 +1778,12 @@ int npfn_engine_create(const npfn_config* cfg, const float* weights, size_t n_we
   HIPCHK(hipGetDeviceCount(&ndev));
   if (cfg->device < 0 || cfg->device >= ndev) return fail(NPFN_EINVAL, "bad device ordinal");
   HIPCHK(hipSetDevice(cfg->device));
+  // the ensemble mix holds a row's bars (and a translated estimator's prefix sums) in LDS
+  if (mix_lds_bytes(cfg->n_bars, true) > mix_lds_limit())
+    return fail(NPFN_EINVAL, "n_bars = " + std::to_string(cfg->n_bars) + " needs " +
+                                 std::to_string(mix_lds_bytes(cfg->n_bars, true)) +
+                                 " B of LDS per workgroup in the ensemble mix, the device grants " +
+                                 std::to_string(mix_lds_limit()));
   npfn_engine* h = new npfn_engine();
   h->cfg = *cfg;
   h->ne = cfg->n_estimators;
@@ -1830,6 +1836,7 @@ int npfn_engine_create(const npfn_config* cfg, const float* weights, size_t n_we
     return rc;
   }
   gemm_setup();
+  mix_setup();
   rowk_setup();
   svd_setup();
   {
@@ -2422,6 +2429,136 @@ int npfn_debug_views(npfn_engine* h, float* out, int64_t rows, int32_t max_cols,
   if ((size_t)rows * h->f->vl.Vw * sizeof(float) > v->bytes) return fail(NPFN_EINVAL, "debug_views: too many rows");
   HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipMemcpy(out, v->p, (size_t)rows * h->f->vl.Vw * sizeof(float), hipMemcpyDeviceToHost));
+  return NPFN_OK;
+}
+
+int npfn_debug_target_translation(npfn_engine* h, int32_t n_bars, int32_t n_est, double* ylam, float* ystats,
+                                  int32_t* idx, float* share, uint8_t* tcancel, int32_t* ett, int32_t* translated) {
+  RCHK(check_engine(h));
+  if (!ylam || !ystats || !idx || !share || !tcancel || !ett || !translated)
+    return fail(NPFN_EINVAL, "debug_target_translation: null pointer");
+  if (n_bars != h->cfg.n_bars || n_est != h->cfg.n_estimators)
+    return fail(NPFN_EINVAL, "debug_target_translation: n_bars / n_est are not the engine's");
+  if (!h->f->fitted || h->f->ncls > 0) return fail(NPFN_ESTATE, "debug_target_translation before a regressor fit");
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(ystats, h->f->ystats.p, 6 * sizeof(float), hipMemcpyDeviceToHost));
+  for (int e = 0; e < n_est; ++e) ett[e] = h->any_tt ? h->h_tt[e] : 0;
+  *translated = h->any_tt ? 1 : 0;
+  if (!h->any_tt) {  // no translation: nothing else is defined
+    *ylam = std::nan("");
+    ystats[3] = ystats[4] = ystats[5] = std::nanf("");
+    return NPFN_OK;
+  }
+  const int nb = n_bars;
+  std::vector<TransEntry> tab((size_t)nb + 1);
+  HIPCHK(hipMemcpy(ylam, h->f->ylam.p, sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(tab.data(), h->f->ttab.p, tab.size() * sizeof(TransEntry), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(tcancel, h->f->tcancel.p, (size_t)nb, hipMemcpyDeviceToHost));
+  for (int b = 0; b <= nb; ++b) {
+    idx[b] = tab[b].idx;
+    share[b] = tab[b].share;
+  }
+  return NPFN_OK;
+}
+
+int npfn_mix_rows(int32_t op, const void* logits, int64_t ld_rows, int64_t row0, int64_t n_rows, int32_t n_est,
+                  int32_t n_bars, float inv_temperature, const int32_t* ett, const void* tab, const uint8_t* tcancel,
+                  int32_t geo, const float* bz, const float* ystats, uint64_t seed, uint64_t counter,
+                  int64_t row_offset, uint64_t philox_row0, int64_t per, float* feat, int64_t ldf, int32_t col,
+                  float* out0, float* out1, int64_t ldo, float log_eps, void* stream) {
+  const char* who = "mix_rows: ";
+  if (op < NPFN_MIX_LOG || op > NPFN_MIX_GROUP_SCORE) return fail(NPFN_EINVAL, std::string(who) + "unknown op");
+  const bool group = op >= NPFN_MIX_GROUP_SAMPLE;
+  const bool tail = op >= NPFN_MIX_SAMPLE;
+  if (n_rows < 0 || n_rows > 0x7fffffffll) return fail(NPFN_EINVAL, std::string(who) + "n_rows outside 0..2^31-1");
+  if (n_bars < 2) return fail(NPFN_EINVAL, std::string(who) + "n_bars must be >= 2");
+  if (!logits) return fail(NPFN_EINVAL, std::string(who) + "null logits");
+  const bool trans = !group && ett != nullptr;
+  if (!group) {
+    if (n_est < 1 || n_est > 64) return fail(NPFN_EINVAL, std::string(who) + "n_est outside 1..64");
+    if (!(inv_temperature > 0.f) || !(inv_temperature < INFINITY))
+      return fail(NPFN_EINVAL, std::string(who) + "inv_temperature must be positive and finite");
+    if ((ett != nullptr) != (tab != nullptr) || (ett != nullptr) != (tcancel != nullptr))
+      return fail(NPFN_EINVAL, std::string(who) + "ett, tab and tcancel must all be given or all be NULL");
+    if (geo != 0 && geo != 1) return fail(NPFN_EINVAL, std::string(who) + "geo must be 0 or 1");
+    if (row0 < 0 || ld_rows < row0 + n_rows)
+      return fail(NPFN_EINVAL, std::string(who) + "rows [row0, row0 + n_rows) do not lie inside ld_rows");
+    if (op != NPFN_MIX_LOG && (row0 != 0 || ld_rows != n_rows))
+      return fail(NPFN_EINVAL, std::string(who) + "only the log op takes a row window (row0, ld_rows)");
+  } else if (per < 1) {
+    return fail(NPFN_EINVAL, std::string(who) + "per must be >= 1");
+  }
+  if (tail) {
+    if (!bz || !ystats || !feat) return fail(NPFN_EINVAL, std::string(who) + "null bz, ystats or feat");
+    if (row_offset < 0 || ldf < 1 || col < 0 || col >= ldf)
+      return fail(NPFN_EINVAL, std::string(who) + "need row_offset >= 0 and 0 <= col < ldf");
+  }
+  const bool is_sample = op == NPFN_MIX_SAMPLE || op == NPFN_MIX_GROUP_SAMPLE;
+  const bool is_score = op == NPFN_MIX_SCORE || op == NPFN_MIX_GROUP_SCORE;
+  if (is_score) {
+    if (!out0 && !out1) return fail(NPFN_EINVAL, std::string(who) + "score needs out0 or out1");
+    if (ldo < 1) return fail(NPFN_EINVAL, std::string(who) + "score needs ldo >= 1");
+  } else if (!is_sample && !out0) {
+    return fail(NPFN_EINVAL, std::string(who) + "null out0");
+  }
+  if (op == NPFN_MIX_LOG && ldo < n_bars) return fail(NPFN_EINVAL, std::string(who) + "log needs ldo >= n_bars");
+  const size_t need = mix_lds_bytes(n_bars, trans), lim = mix_lds_limit();
+  if (need > lim)
+    return fail(NPFN_EINVAL, std::string(who) + "n_bars = " + std::to_string(n_bars) + " needs " +
+                                 std::to_string(need) + " B of LDS per workgroup, the device grants " +
+                                 std::to_string(lim));
+  if (n_rows == 0) return NPFN_OK;
+  static thread_local int setup_dev = -1;
+  int dev = 0;
+  HIPCHK(hipGetDevice(&dev));
+  if (setup_dev != dev) {
+    mix_setup();
+    setup_dev = dev;
+  }
+  HIPCHK(hipGetLastError());  // an earlier launch's error is not this call's
+  MixTrans tr;
+  tr.geo = geo;
+  if (trans) {
+    tr.ett = (const int*)ett;
+    tr.tab = (const TransEntry*)tab;
+    tr.tcancel = tcancel;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const logit_t* lg = (const logit_t*)logits;
+  const float* pr = (const float*)logits;
+  const int nb = n_bars;
+  switch (op) {
+    case NPFN_MIX_LOG:
+      launch_mix_log_rows(lg, ld_rows, row0, n_rows, n_est, nb, inv_temperature, tr, out0, ldo, s);
+      break;
+    case NPFN_MIX_PROB:
+      launch_mix_prob(lg, n_rows, n_est, nb, inv_temperature, tr, out0, s);
+      break;
+    case NPFN_MIX_SAMPLE:
+      launch_mix_sample(lg, n_rows, n_est, nb, inv_temperature, tr, bz, ystats, seed, counter, row_offset, philox_row0,
+                        feat, ldf, col, out0, log_eps, s);
+      break;
+    case NPFN_MIX_NLL:
+      launch_mix_nll(lg, n_rows, n_est, nb, inv_temperature, tr, bz, ystats, row_offset, feat, ldf, col, out0, log_eps,
+                     s);
+      break;
+    case NPFN_MIX_SCORE:
+      launch_mix_score(lg, n_rows, n_est, nb, inv_temperature, tr, bz, ystats, row_offset, feat, ldf, col, out0, out1,
+                       ldo, log_eps, s);
+      break;
+    case NPFN_MIX_GROUP_SAMPLE:
+      launch_group_sample(pr, per, n_rows, nb, bz, ystats, seed, counter, row_offset, philox_row0, feat, ldf, col, out0,
+                          log_eps, s);
+      break;
+    case NPFN_MIX_GROUP_NLL:
+      launch_group_nll(pr, per, n_rows, nb, bz, ystats, row_offset, feat, ldf, col, out0, log_eps, s);
+      break;
+    default:
+      launch_group_score(pr, per, n_rows, nb, bz, ystats, row_offset, feat, ldf, col, out0, out1, ldo, log_eps, s);
+      break;
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(NPFN_EHIP, std::string(who) + "launch: " + hipGetErrorString(e));
   return NPFN_OK;
 }
 

@@ -265,6 +265,11 @@ struct MixTrans {
   int geo = 0;                        // 1: tabpfn's average_before_softmax -- the mixture is
                                       // softmax(mean_e log q_e) instead of mean_e q_e
 };
+// LDS one k_mix_* / k_group_* workgroup needs for nb bars (static arrays included), what the
+// current device grants a workgroup, and the per-kernel grant of dynamic LDS above 64 KiB
+size_t mix_lds_bytes(int nb, bool translated);
+size_t mix_lds_limit();
+void mix_setup();
 void launch_mix_log(const logit_t* logits, int64_t R, int E, int nb, float invT, const MixTrans& tr, float* out,
                     int64_t ldo, hipStream_t s);
 void launch_mix_sample(const logit_t* logits, int64_t R, int E, int nb, float invT, const MixTrans& tr,

@@ -2533,6 +2533,13 @@ __device__ void mix_row_fast(const logit_t* __restrict__ logits, int64_t R, int6
     float M = rb[0], S = rb[4];
 #pragma unroll
     for (int k = 1; k < 4; ++k) ms_merge(M, S, rb[k], rb[4 + k]);
+    if (M == -INFINITY) {  // no finite logit (block-uniform): the estimator has no mass to give --
+      if (tr.geo) {        // nothing to the mean, log 0 to every bar of the mean of logs
+#pragma unroll
+        for (int j = 0; j < NV; ++j) acc[j] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+      }
+      continue;
+    }
     if (!trans) {
       if (tr.geo) {  // average_before_softmax: mean of the log probabilities
         // the exact log-softmax, x / T - M - log S, from the logits re-read (L2) -- not log of the
@@ -2641,6 +2648,11 @@ __device__ void mix_row(const logit_t* __restrict__ logits, int64_t R, int64_t r
     float mx = -INFINITY;
     for (int b = tid; b < nb; b += 256) mx = fmaxf(mx, lv(b));
     mx = block_reduce_max(mx, red);
+    if (mx == -INFINITY) {  // no finite logit (block-uniform): no mass to give, as on the fast path
+      if (tr.geo)
+        for (int b = tid; b < nb; b += 256) p[b] = -INFINITY;
+      continue;
+    }
     float s = 0.f;
     for (int b = tid; b < nb; b += 256) s += __expf(lv(b) - mx);
     s = block_reduce_sum(s, red);
@@ -2744,6 +2756,11 @@ __device__ void bar_sample_row(const float* __restrict__ p, const float* __restr
   if (found >= 0 && found == s_idx) s_cprev = cfound;
   __syncthreads();
   if (tid == 0) {
+    if (!(total > 0.f) || !(total < INFINITY)) {  // a row with no mass: NaN, as bar_stats_row
+      theta_out = NAN;
+      logp_out = NAN;
+      return;
+    }
     int idx = s_idx;
     float cprev = s_cprev;
     if (idx == 0x7fffffff) {  // u beyond the rounded total: the last bar with mass
@@ -3843,6 +3860,46 @@ static size_t mix_smem(int nb, const MixTrans& tr) {
     else if ((nb + 1023) / 1024 <= 5) hipLaunchKernelGGL(KERNEL<5>, g_, b_, sm_, s, __VA_ARGS__);     \
     else hipLaunchKernelGGL(KERNEL<kMixV4>, g_, b_, sm_, s, __VA_ARGS__);                             \
   } while (0)
+
+// LDS of one k_mix_* workgroup for nb bars: the dynamic part plus kMixStaticLds for the kernels'
+// static arrays (step_sample's scan[256], scan4 and the sampler's three words: 1052 B, rounded up)
+constexpr size_t kMixStaticLds = 2048;
+size_t mix_lds_bytes(int nb, bool translated) {
+  MixTrans t;
+  static const int one = 1;
+  if (translated) t.ett = &one;
+  return mix_smem(nb, t) + kMixStaticLds;
+}
+// what a workgroup of the current device may hold (hipDeviceAttributeMaxSharedMemoryPerBlock);
+// 64 KiB, which every launch is granted, when no device answers
+size_t mix_lds_limit() {
+  int dev = 0, v = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || v <= 0) {
+    (void)hipGetLastError();
+    return 65536;
+  }
+  return (size_t)v;
+}
+// dynamic LDS above 64 KiB has to be granted per kernel function (as gemm_setup does for the GEMMs)
+#define NPFN_MIX_ATTR(KERNEL)                                                                          \
+  (void)hipFuncSetAttribute((const void*)KERNEL<0>, hipFuncAttributeMaxDynamicSharedMemorySize, dyn);  \
+  (void)hipFuncSetAttribute((const void*)KERNEL<5>, hipFuncAttributeMaxDynamicSharedMemorySize, dyn);  \
+  (void)hipFuncSetAttribute((const void*)KERNEL<kMixV4>, hipFuncAttributeMaxDynamicSharedMemorySize, dyn);
+void mix_setup() {
+  const size_t lim = mix_lds_limit();
+  if (lim <= 65536) return;
+  const int dyn = (int)(lim - kMixStaticLds);
+  NPFN_MIX_ATTR(k_mix_log)
+  NPFN_MIX_ATTR(k_mix_prob)
+  NPFN_MIX_ATTR(k_mix_sample)
+  NPFN_MIX_ATTR(k_mix_nll)
+  NPFN_MIX_ATTR(k_mix_score)
+  (void)hipFuncSetAttribute((const void*)k_group_sample, hipFuncAttributeMaxDynamicSharedMemorySize, dyn);
+  (void)hipFuncSetAttribute((const void*)k_group_nll, hipFuncAttributeMaxDynamicSharedMemorySize, dyn);
+  (void)hipFuncSetAttribute((const void*)k_group_score, hipFuncAttributeMaxDynamicSharedMemorySize, dyn);
+  (void)hipGetLastError();
+}
 
 void launch_mix_log(const logit_t* logits, int64_t R, int E, int nb, float invT, const MixTrans& tr, float* out,
                     int64_t ldo, hipStream_t s) {

@@ -19,7 +19,7 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 import torch
 
-from .limits import check_engine_table
+from .limits import check_engine_table, check_n_bars
 from .weights import ModelConfig, pack_weights, synthetic_weights
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_lib", "libnpfn.so")
@@ -134,6 +134,11 @@ SIGNATURES = {
     "npfn_prof_enable": (ctypes.c_int, [_vp, ctypes.c_int]),
     "npfn_prof_read": (ctypes.c_int, [_vp, ctypes.POINTER(NpfnProfEntry), _i32, ctypes.POINTER(_i32)]),
     "npfn_debug_views": (ctypes.c_int, [_vp, _vp, _i64, _i32, ctypes.POINTER(_i32)]),
+    "npfn_debug_target_translation": (ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, ctypes.POINTER(_i32), _vp, _vp,
+                                                     ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
+    "npfn_mix_rows": (ctypes.c_int, [_i32, _vp, _i64, _i64, _i64, _i32, _i32, _f, ctypes.POINTER(_i32), _vp, _vp, _i32,
+                                     _vp, _vp, _u64, _u64, _i64, _u64, _i64, _vp, _i64, _i32, _vp, _vp, _i64, _f,
+                                     _vp]),
     "npfn_debug_item_attn_online": (ctypes.c_int, [ctypes.c_int]),
     "npfn_debug_item_attn_scale": (ctypes.c_int, [_f]),
     "npfn_debug_fail_row_launch": (ctypes.c_int, [_vp, _i32]),
@@ -303,6 +308,71 @@ def w2_assign(a, b, scale, lib=None):
     return assign, duals, cost_sum, steps, bad
 
 
+MIX_OPS = {"log": 0, "prob": 1, "sample": 2, "nll": 3, "score": 4,   # npfn.h NPFN_MIX_*
+           "group_sample": 5, "group_nll": 6, "group_score": 7}
+
+
+def pack_translation(idx, share, tcancel, device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Device buffers of a translation table as npfn_mix_rows reads them: ``tab`` [n_bars + 1, 2]
+    int32 (idx, the bits of the float32 share) and ``tcancel`` padded to n_bars + 4 bytes."""
+    idx = np.ascontiguousarray(idx, dtype=np.int32)
+    share = np.ascontiguousarray(share, dtype=np.float32)
+    tc = np.ascontiguousarray(tcancel, dtype=np.uint8)
+    if idx.ndim != 1 or share.shape != idx.shape or tc.shape != (idx.shape[0] - 1,):
+        raise ValueError(f"pack_translation: idx {idx.shape}, share {share.shape} and tcancel {tc.shape} are not "
+                         "[n_bars + 1], [n_bars + 1] and [n_bars]")
+    tab = np.stack([idx, share.view(np.int32)], axis=1)
+    return (torch.from_numpy(tab).to(device), torch.from_numpy(np.concatenate([tc, np.zeros(4, np.uint8)])).to(device))
+
+
+def mix_rows(op: str, logits: torch.Tensor, *, n_bars: Optional[int] = None, inv_temperature: float = 1.0,
+             ett=None, tab: Optional[torch.Tensor] = None, tcancel: Optional[torch.Tensor] = None, geo: bool = False,
+             bz: Optional[torch.Tensor] = None, ystats: Optional[torch.Tensor] = None, seed: int = 0,
+             counter: int = 0, row_offset: int = 0, philox_row0: int = 0, per: int = 1,
+             feat: Optional[torch.Tensor] = None, col: int = 0, out0: Optional[torch.Tensor] = None,
+             out1: Optional[torch.Tensor] = None, ldo: Optional[int] = None, row0: int = 0,
+             n_rows: Optional[int] = None, log_eps: float = math.log(1e-15), lib=None):
+    """npfn_mix_rows (include/npfn.h; needs no engine) on the GPU that holds ``logits``: fp16
+    [n_est, ld_rows, n_bars] for the mix ops, a float32 "prob" result [*, n_bars] for the group
+    ops.  ``tab`` / ``tcancel`` come from :func:`pack_translation`, ``ett`` is a list or an int32
+    device tensor.  "log" and "prob" allocate and return their output; the tails write ``feat``
+    [*, ldf] / ``out0`` / ``out1`` in place and return ``(out0, out1)``.  The C call's own
+    argument checks are the only ones."""
+    code = MIX_OPS[op]
+    group = code >= 5
+    dev = logits.device
+    lib = lib or load_library()
+    if group:
+        nb = logits.shape[-1]
+        E, ld_rows = 1, 0
+        if n_rows is None:
+            raise ValueError("mix_rows: the group ops need n_rows")
+    else:
+        E, ld_rows, nb = logits.shape
+        if n_rows is None:
+            n_rows = ld_rows - row0
+    if n_bars is not None:
+        nb = n_bars
+    if isinstance(ett, (list, tuple, np.ndarray)):
+        ett = torch.as_tensor(np.asarray(ett, dtype=np.int32)).to(dev)
+    if code == 0 and out0 is None:
+        ldo = nb if ldo is None else ldo
+        out0 = torch.empty((n_rows, ldo), dtype=torch.float32, device=dev)
+    if code == 1 and out0 is None:
+        out0 = torch.empty((n_rows, nb), dtype=torch.float32, device=dev)
+    ldo = (nb if code == 0 else 1) if ldo is None else ldo
+    ldf = feat.shape[-1] if feat is not None else 1
+    ettp = None if ett is None else ctypes.cast(ctypes.c_void_p(ett.data_ptr()), ctypes.POINTER(_i32))
+    with torch.cuda.device(dev):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _check(lib, lib.npfn_mix_rows(code, _ptr(logits), ld_rows, row0, n_rows, E, nb, float(inv_temperature), ettp,
+                                      _ptr(tab), _ptr(tcancel), int(geo), _ptr(bz), _ptr(ystats),
+                                      int(seed) & 0xFFFFFFFFFFFFFFFF, int(counter), int(row_offset), int(philox_row0),
+                                      int(per), _ptr(feat), ldf, int(col), _ptr(out0), _ptr(out1), int(ldo),
+                                      float(log_eps), stream), "npfn_mix_rows")
+    return out0 if code <= 1 else (out0, out1)
+
+
 MAX_QUANTILES = 64  # npfn_bar_stats / npfn_predict_stats take at most this many levels per call
 
 
@@ -334,6 +404,7 @@ class Engine:
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         if self.device.type != "cuda":
             raise EngineError(f"engine device must be a GPU, got {self.device}")
+        check_n_bars(cfg.n_bars)
         if weights is None:
             weights = synthetic_weights(cfg, seed=0)
         blob = _packed(weights, cfg)
@@ -1083,6 +1154,36 @@ class Engine:
         _check(self.lib, self.lib.npfn_debug_views(self.h, buf.ctypes.data_as(ctypes.c_void_p), int(rows),
                                                    int(max_cols), ctypes.byref(vw)), "npfn_debug_views")
         return buf.reshape(-1)[: int(rows) * vw.value].reshape(int(rows), vw.value).copy()
+
+    def debug_target_translation(self) -> dict:
+        """The last regressor fit's target-border translation on the host
+        (npfn_debug_target_translation; synchronous): ``ylam``, ``ystats`` [6], ``idx`` / ``share``
+        [n_bars + 1], ``tcancel`` [n_bars], ``ett`` [n_estimators] and ``translated``; without a
+        target-transforming estimator ``translated`` is False and the tables are None."""
+        nb, E = self.cfg.n_bars, self.cfg.n_estimators
+        ylam = ctypes.c_double()
+        ystats = np.zeros(6, np.float32)
+        idx, share = np.zeros(nb + 1, np.int32), np.zeros(nb + 1, np.float32)
+        tc, ett = np.zeros(nb, np.uint8), np.zeros(E, np.int32)
+        tr = _i32(0)
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+        ip = lambda a: a.ctypes.data_as(ctypes.POINTER(_i32))  # noqa: E731
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.npfn_debug_target_translation(
+                self.h, nb, E, ctypes.cast(ctypes.byref(ylam), ctypes.c_void_p), vp(ystats), ip(idx), vp(share),
+                vp(tc), ip(ett), ctypes.byref(tr)), "npfn_debug_target_translation")
+        on = bool(tr.value)
+        return {"translated": on, "ylam": ylam.value, "ystats": ystats, "ett": ett, "idx": idx if on else None,
+                "share": share if on else None, "tcancel": tc if on else None}
+
+    def mix_translation(self):
+        """``(ett, tab, tcancel)`` device buffers of the last fit for :func:`mix_rows`, or three
+        None when nothing is translated."""
+        t = self.debug_target_translation()
+        if not t["translated"]:
+            return None, None, None
+        tab, tc = pack_translation(t["idx"], t["share"], t["tcancel"], self.device)
+        return torch.from_numpy(t["ett"]).to(self.device), tab, tc
 
     def debug_item_attn_online(self, on: bool = True) -> None:
         """Process-wide: every item-attention block also runs its online-softmax fallback pass

@@ -39,6 +39,32 @@ T_RAW, T_QUANT, T_POWER, T_QSVD, T_PFP, T_RFP = 0, 1, 2, 3, 4, 5
 MODES = {"none": 0, "quantile": 1, "quantile+power": 2, "ensemble": 3}
 
 
+MIX_LDS_LIMIT = 160 * 1024       # LDS a workgroup may hold on gfx950 (the C side asks the device)
+MIX_FAST_MAX_BARS = 8192         # mix_fast: n_bars % 4 == 0 up to 256 * 4 * kMixV4
+MIX_STATIC_LDS = 2048            # kMixStaticLds
+
+
+def mix_lds_bytes(n_bars: int, translated: bool = True) -> int:
+    """LDS of one ensemble-mix workgroup (csrc/npfn_kernels.hip ``mix_lds_bytes``): 64 B of
+    reduction scratch, the row's masses, a translated estimator's (mass, prefix sum) pairs --
+    overlaid on the masses by the register path -- and the kernels' static arrays."""
+    pb = (n_bars * 4 + 15) & ~15
+    pcb = n_bars * 8 if translated else 0
+    fast = n_bars % 4 == 0 and n_bars <= MIX_FAST_MAX_BARS
+    return 64 + (max(pb, pcb) if fast else pb + pcb) + MIX_STATIC_LDS
+
+
+def check_n_bars(n_bars: int, lds_limit: int = MIX_LDS_LIMIT) -> None:
+    """ValueError when the ensemble mix cannot hold a row of ``n_bars`` bars in a workgroup's LDS
+    (npfn_engine_create returns NPFN_EINVAL for the same n_bars)."""
+    if n_bars < 2:
+        raise ValueError(f"n_bars must be at least 2, got {n_bars}")
+    need = mix_lds_bytes(n_bars)
+    if need > lds_limit:
+        raise ValueError(f"n_bars = {n_bars} needs {need} B of LDS per workgroup in the ensemble mix; a workgroup "
+                         f"holds at most {lds_limit} B")
+
+
 def check_pretraining_limits(n_rows: int, n_features: int, ignore_pretraining_limits: bool) -> None:
     """tabpfn's ``ValueError`` for more than 10 000 rows / 500 features [ext]."""
     if ignore_pretraining_limits:
