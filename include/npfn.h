@@ -563,6 +563,66 @@ int npfn_w2_assign(const float* a, const float* b, int64_t n_obs, int32_t n, int
                    const double* scale, int32_t* assign, int64_t* duals, int64_t* cost_sum,
                    int64_t* steps, int32_t* bad, void* stream);
 
+/* Classifier two-sample test (npe_pfn.diagnostics.c2st_batched; the reference's
+ * classifier_two_samples_test_torch, scripts/evaluate_ropefm.py:119-280; needs no engine): per
+ * (observation, fold) a small ReLU MLP is trained with Adam on the pooled points outside the fold
+ * and scored on the points inside it, all in one launch.  z [n_obs, n_pool, dim] (device): per
+ * observation the pooled sample; points 0..n_first-1 have label 0, the others label 1.  widths
+ * (HOST) [n_layers + 1]: widths[0] = dim, widths[n_layers] = 2; layer l is a Linear of widths[l]
+ * inputs and widths[l + 1] units, a ReLU behind every layer but the last.  init [P] (device): the
+ * starting parameters of every (observation, fold), layer by layer W [out, in] row-major then b
+ * [out]; P = sum of widths[l + 1] * (widths[l] + 1).  fold [n_pool] uint8 (device): the fold that
+ * holds each point out.  order [n_folds, epochs, order_ld] int32 (device): row (f, e) lists, in its
+ * first n_train[f] entries (n_train HOST [n_folds]), the pooled indices that fold f trains on in
+ * epoch e, in visiting order (indices are clamped to 0..n_pool-1); batch j of an epoch is entries j
+ * * batch .. min((j + 1) * batch, n_train[f]) - 1, a short last batch included.  adam [n_steps, 2]
+ * float (device), n_steps >= epochs * ceil(max n_train / batch): for step t (0-based, counted over
+ * the batches of all epochs) adam[t] = (lr / (1 - beta1^(t+1)), 1 / sqrt(1 - beta2^(t+1))).
+ * Outputs (device), ZEROED BY THE CALL itself on `stream`: correct [n_obs, n_folds] int32, loss
+ * [n_obs, n_folds, epochs], prob [n_obs, n_pool] (may be NULL), params_out [n_obs, n_folds, P] (may
+ * be NULL), bad [n_obs] int32.  Everything in fp32, sums as chains of fmaf:
+ *  - forward, per row: h_0 = the point; unit o of layer l = sum over i ascending of W[o][i] h_l[i],
+ *    then + b[o]; h_{l+1} = the unit where it is >= 0, else 0; the last layer's two units are the
+ *    logits (l0, l1), d = l1 - l0;
+ *  - row loss = max(s, 0) + log1pf(expf(-|s|)), s = d for label 0 and -d for label 1 (cross-
+ *    entropy); p1 = 1 / (1 + expf(-d)) (as e / (1 + e), e = expf(d), for d < 0); the error of logit
+ *    1 is (p1 - label) / B and of logit 0 its negative, B the rows of the batch; the batch loss is
+ *    (the row losses added in row order) / B, an epoch adds batch loss * B over its batches, and
+ *    loss[u][f][e] = that / n_train[f] (the reference's epoch_loss / len(train_ds));
+ *  - backward: the error of unit i of layer l = sum over o ascending of error_{l+1}[o] W_l[o][i]
+ *    where h_l[i] > 0, else 0; dW[o][i] = sum over the batch's rows in order of error[o] h[i], db[o]
+ *    likewise with h = 1;
+ *  - Adam as torch.optim.Adam (no amsgrad): g = dW + weight_decay * w; m = beta1 m + (1 - beta1) g;
+ *    v = beta2 v + (1 - beta2) g g; w -= adam[t][0] * (m / (sqrt(v) * adam[t][1] + eps)), 1 - beta
+ *    formed in fp32 from the fp32 beta, sqrt and the division correctly rounded;
+ *  - after the last epoch, for every point i with fold[i] == f: prob[u][i] = p1 of the fold's
+ *    network, and correct[u][f] counts the points whose prediction (1 exactly when l1 > l0) equals
+ *    their label.
+ * bad[u] = 1 for a non-finite coordinate (nothing is trained), 2 when an epoch loss of some fold
+ * is not finite; the observation's other outputs are then unspecified.  The result of an
+ * (observation, fold) is bitwise the same from run to run and whatever other observations are in
+ * the call: no atomics, every sum in the order above (npe_pfn.diagnostics.c2st_fit_host restates
+ * it in torch, to rounding).
+ * Kernel: one workgroup of 512 threads per (observation, fold).  Each layer's [W | b] sits in LDS
+ * padded to a multiple of 4 rows and columns (padding entries are parameters that stay 0); a batch
+ * is processed in tiles of 16 rows, whose activations and errors per layer are in LDS; the 4 x 4
+ * tiles of all layers' padded [W | b] are dealt to the threads, at most 3 each, and a thread keeps
+ * the gradient and both Adam moments of its 48 entries in registers for the whole training.  Batch
+ * rows are read from global memory.  Asynchronous; n_obs == 0 launches nothing.
+ * Caps: P <= 16384 and every width <= 128 -- "mlp" (dim, 4 dim, 8 dim, 8 dim, 4 dim, 2) up to dim
+ * 11, "mlp_small" (dim, 4 dim, 4 dim, 2) up to dim 28, "linear" (dim, 2) up to dim 64.
+ * Errors (host, before any launch): NPFN_EINVAL (message starting "c2st_fit") for n_obs < 0, dim
+ * outside 1..64, n_pool outside 2..32768, n_first outside 1..n_pool-1, n_layers outside 1..5,
+ * widths[0] != dim, a last width != 2, a width outside 1..128, P > 16384, n_folds outside 2..16,
+ * epochs < 1, batch outside 1..4096, an n_train outside 1..min(order_ld, n_pool), or a missing z,
+ * widths, init, fold, order, n_train, adam, correct, loss or bad. */
+int npfn_c2st_fit(const float* z, int64_t n_obs, int32_t n_pool, int32_t n_first, int32_t dim,
+                  const int32_t* widths, int32_t n_layers, const float* init, const uint8_t* fold,
+                  int32_t n_folds, const int32_t* order, const int32_t* n_train, int32_t order_ld,
+                  int32_t epochs, int32_t batch, const float* adam, float beta1, float beta2,
+                  float eps, float weight_decay, int32_t* correct, float* loss, float* prob,
+                  float* params_out, int32_t* bad, void* stream);
+
 /* K12 standardized-Euclidean context filter (support_posterior.py:357-369):
  * idx_out[0:k] = indices of the k rows of x [n_rows, dim] closest to obs in
  * z-scored Euclidean distance, ascending (ties by lower index). */

@@ -21,6 +21,12 @@ Exact 2-Wasserstein distance between two equally sized sets of draws (``wasserst
 ``NPE_PFN_Core.wasserstein_batched``): the reference harness's ``sqrt(ot.emd2(...))`` as a linear
 assignment problem on integer costs.  ``transport_costs_host`` and ``assignment_solve_host`` are
 the definition of the engine's ``npfn_w2_assign``, ``TransportResult`` what comes back.
+
+Classifier two-sample test (``c2st_batched``, ``NPE_PFN_Core.c2st_batched``): the reference
+harness's C2ST, a small MLP per fold trained to tell the two sets apart, 0.5 = indistinguishable.
+``c2st_folds``, ``c2st_order``, ``c2st_widths``, ``c2st_init`` and ``c2st_adam_table`` fix every
+random and tabulated input on the host, ``c2st_fit_host`` is the definition of the engine's
+``npfn_c2st_fit``, ``ClassifierTestResult`` what comes back.
 """
 
 from __future__ import annotations
@@ -33,7 +39,8 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from .engine import MMD_MAX_LABELLINGS, check_mmd_args, check_transport_args
+from .engine import (C2ST_BETAS, C2ST_EPS, C2ST_MAX_FOLDS, MMD_MAX_LABELLINGS, check_c2st_args, check_mmd_args,
+                     check_transport_args)
 
 HALFNORMAL_MEDIAN = 0.6744897501960817  # median of |N(0, 1)|: the tail bars' scale is width / this
 
@@ -358,6 +365,13 @@ def mmd_p_value(observed: Tensor, null: Tensor) -> Tensor:
     return torch.where(torch.isnan(observed), torch.full_like(p, float("nan")), p)
 
 
+def _standardise(z: Tensor, a: Tensor) -> Tensor:
+    """``z`` [M, N, d] by the per-observation mean and unbiased std of ``a`` [M, n, d]; a zero std
+    counts as 1 (the reference's C2ST z-score)."""
+    mu, sd = a.mean(1, keepdim=True), a.std(1, keepdim=True)
+    return (z - mu) / torch.where(sd == 0, torch.ones_like(sd), sd)
+
+
 def mmd_batched(a, b, kernel: str = "rbf", bandwidths=None, num_permutations: int = 0, seed: int = 0,
                 z_score: bool = False, engine=None) -> TwoSampleResult:
     """MMD two-sample test between ``a`` [M, n, d] and ``b`` [M, m, d], observation by observation
@@ -397,8 +411,7 @@ def mmd_batched(a, b, kernel: str = "rbf", bandwidths=None, num_permutations: in
     z = torch.cat([a, b], 1)
     _, bw = check_mmd_args(z.shape, (P + 1, n + m), kernel, bw)
     if z_score:
-        mu, sd = a.mean(1, keepdim=True), a.std(1, keepdim=True)
-        z = (z - mu) / torch.where(sd == 0, torch.ones_like(sd), sd)
+        z = _standardise(z, a)
     labels = permutation_labels(n, m, P, seed)
     if dev.type == "cuda":
         from .engine import mmd_sums
@@ -624,3 +637,270 @@ def wasserstein_batched(a, b, z_score: bool = False, engine=None) -> TransportRe
     w2 = torch.where(nan, torch.full_like(w2, float("nan")), w2)
     assign = torch.where(nan[:, None], torch.full_like(assign, -1), assign)
     return TransportResult(torch.sqrt(w2), w2, assign, cost_sum, scale, steps, n)
+
+
+# ------------------------------------------------------------------ classifier two-sample test
+C2ST_MODELS = ("mlp", "mlp_small", "linear")   # the reference's _MODEL_REGISTRY
+
+
+def c2st_folds(n: int, m: int, n_folds: int = 5, seed: int = 1) -> Tensor:
+    """Stratified, shuffled folds of n + m pooled points: uint8 [n + m] (CPU), the fold that holds
+    each point out.  With p = ``torch.randperm(n)`` and then q = ``torch.randperm(m)`` of a CPU
+    ``torch.Generator`` seeded with ``seed``, point p[i] of the first set gets fold i % n_folds and
+    point n + q[i] of the second fold (i + n) % n_folds, so fold sizes differ by at most one overall
+    and per class, and a seed gives the same folds on every machine."""
+    n, m, F = int(n), int(m), int(n_folds)
+    if not 2 <= F <= C2ST_MAX_FOLDS:
+        raise ValueError(f"c2st_folds: n_folds must lie in 2..{C2ST_MAX_FOLDS}, got {F}")
+    if n < F or m < F:
+        raise ValueError(f"c2st_folds: need at least n_folds = {F} points in each set, got {n} and {m}")
+    gen = torch.Generator().manual_seed(int(seed))
+    p, q = torch.randperm(n, generator=gen), torch.randperm(m, generator=gen)
+    fold = torch.empty(n + m, dtype=torch.uint8)
+    fold[p] = (torch.arange(n) % F).to(torch.uint8)
+    fold[n + q] = ((torch.arange(m) + n) % F).to(torch.uint8)
+    return fold
+
+
+def c2st_order(n_pool: int, epochs: int, seed: int) -> Tensor:
+    """Visiting order of the pooled points per epoch: int32 [epochs, n_pool] (CPU), row e the e-th
+    ``torch.randperm(n_pool)`` of a CPU ``torch.Generator`` seeded with ``seed``.  Fold f visits
+    epoch e's row in that order and skips its own held-out points; batches are consecutive runs of
+    ``batch_size`` of what is left, a short last batch kept (as the reference's DataLoader does)."""
+    n_pool, epochs = int(n_pool), int(epochs)
+    if n_pool < 1 or epochs < 1:
+        raise ValueError(f"c2st_order: need n_pool >= 1 and epochs >= 1, got {n_pool} and {epochs}")
+    gen = torch.Generator().manual_seed(int(seed))
+    return torch.stack([torch.randperm(n_pool, generator=gen) for _ in range(epochs)]).to(torch.int32)
+
+
+def c2st_widths(model: str, d: int) -> list:
+    """Layer widths of the reference's classifiers on d inputs: "mlp" [d, 4d, 8d, 8d, 4d, 2]
+    (DefaultMLP), "mlp_small" [d, 4d, 4d, 2], "linear" [d, 2]."""
+    d = int(d)
+    if model == "mlp":
+        return [d, 4 * d, 8 * d, 8 * d, 4 * d, 2]
+    if model == "mlp_small":
+        return [d, 4 * d, 4 * d, 2]
+    if model == "linear":
+        return [d, 2]
+    raise ValueError(f"c2st_widths: model must be one of {C2ST_MODELS}, got {model!r}")
+
+
+def c2st_init(widths, seed: int) -> Tensor:
+    """Starting parameters of the MLP with these ``widths``: float32 [P] (CPU), layer by layer W
+    [out, in] row-major then b [out], each uniform in +-1 / sqrt(in) (``torch.nn.Linear``'s default)
+    from a CPU ``torch.Generator`` seeded with ``seed``.  The same vector starts every fold of every
+    observation."""
+    gen = torch.Generator().manual_seed(int(seed))
+    parts = []
+    for fan_in, out in zip(widths[:-1], widths[1:]):
+        bound = 1.0 / math.sqrt(int(fan_in))
+        for shape in ((int(out), int(fan_in)), (int(out),)):
+            parts.append(((torch.rand(shape, generator=gen, dtype=torch.float64) * 2 - 1) * bound).reshape(-1))
+    return torch.cat(parts).to(torch.float32)
+
+
+def c2st_adam_table(lr: float, n_steps: int, dtype=torch.float32) -> Tensor:
+    """Adam's per-step factors, float32 [n_steps, 2] (CPU): row t (step t + 1) is (lr / (1 -
+    beta1^(t+1)), 1 / sqrt(1 - beta2^(t+1))) with torch's default betas, computed in fp64 and
+    rounded once.  The engine and ``c2st_fit_host`` at float32 read the same table;
+    ``c2st_fit_host`` at float64 asks for it unrounded (``dtype=torch.float64``), since the
+    rounding of the step size alone moves a loss by 1e-9 within a few dozen steps."""
+    t = torch.arange(1, int(n_steps) + 1, dtype=torch.float64)
+    b1, b2 = C2ST_BETAS
+    return torch.stack([float(lr) / (1.0 - b1 ** t), 1.0 / torch.sqrt(1.0 - b2 ** t)], 1).to(dtype)
+
+
+def c2st_fit_host(z, n_first, fold, order, widths, init, epochs, batch_size=128, lr=1e-3, weight_decay=0.0,
+                  dtype=torch.float32) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """``(correct [M, F] int32, loss [M, F, E], prob [M, N], bad [M] int32)`` (CPU) -- the
+    definition of the engine's ``npfn_c2st_fit`` (``engine.c2st_fit``, same arguments), in plain
+    torch matmuls at ``dtype`` (float32 or float64).
+
+    ``z`` [M, N, d] is every observation's pooled sample; points 0..n_first-1 have label 0, the
+    rest label 1.  Per observation and fold f (``fold`` [N]) the MLP of ``widths`` starts at
+    ``init`` and is trained for ``epochs`` passes: epoch e visits row e of ``order`` [E, N] without
+    the points of fold f, in batches of ``batch_size`` (a short last batch kept).  Per batch of B
+    rows: logits (l0, l1) from Linear / ReLU layers, d = l1 - l0, row loss max(s, 0) + log1p(exp(-
+    |s|)) with s = d for label 0 and -d for label 1 (cross-entropy), batch loss their mean; the
+    gradient is back-propagated from (sigmoid(d) - label) / B; Adam as ``torch.optim.Adam`` (betas
+    0.9 / 0.999, eps 1e-8, no amsgrad, ``weight_decay`` added to the gradient), 1 - beta formed at
+    ``dtype``, the step's bias corrections from :func:`c2st_adam_table` at ``dtype``.  loss[., f, e] = (sum over
+    the batches of batch loss * B) / n_train, the reference's epoch_loss / len(train_ds).  After
+    the last epoch every point of fold f gets prob = sigmoid(d) under this network and counts as
+    correct when its prediction (1 exactly when l1 > l0; a tie is 0, as argmax) is its label.
+    bad = 1 for a non-finite coordinate (zero outputs), 2 when an epoch loss is not finite."""
+    z = torch.as_tensor(z).detach().to(device="cpu", dtype=dtype)
+    fold = torch.as_tensor(fold).detach().cpu().to(torch.int64)
+    order = torch.as_tensor(order).detach().cpu().to(torch.int64)
+    init = torch.as_tensor(init).detach().to(device="cpu", dtype=dtype)
+    F = int(fold.max()) + 1
+    E, bs = int(epochs), int(batch_size)
+    M, N, d, P = check_c2st_args(z.shape, n_first, widths, F, E, bs)
+    if tuple(fold.shape) != (N,) or tuple(order.shape) != (E, N) or tuple(init.shape) != (P,):
+        raise ValueError(f"c2st_fit_host: fold {tuple(fold.shape)}, order {tuple(order.shape)} and init "
+                         f"{tuple(init.shape)} are not [{N}], [{E}, {N}] and [{P}]")
+    widths = [int(w) for w in widths]
+    L = len(widths) - 1
+    label = (torch.arange(N) >= int(n_first)).to(dtype)
+    finite = torch.isfinite(z).all(2).all(1)
+    zz = torch.where(finite[:, None, None], z, torch.zeros_like(z))
+    b1, b2 = torch.tensor(C2ST_BETAS[0], dtype=dtype), torch.tensor(C2ST_BETAS[1], dtype=dtype)
+    omb1, omb2 = 1 - b1, 1 - b2
+    eps, wd = torch.tensor(C2ST_EPS, dtype=dtype), torch.tensor(float(weight_decay), dtype=dtype)
+    n_train = [N - int((fold == f).sum()) for f in range(F)]
+    table = c2st_adam_table(lr, E * ((max(n_train) + bs - 1) // bs), dtype=dtype)
+
+    correct = torch.zeros((M, F), dtype=torch.int32)
+    loss = torch.zeros((M, F, E), dtype=dtype)
+    prob = torch.zeros((M, N), dtype=dtype)
+
+    def forward(params, x):
+        hs = [x]
+        for l, (W, b) in enumerate(params):
+            h = hs[-1] @ W.transpose(1, 2) + b[:, None, :]
+            hs.append(torch.relu(h) if l + 1 < L else h)
+        return hs
+
+    for f in range(F):
+        params, off = [], 0
+        for i, o in zip(widths[:-1], widths[1:]):
+            W = init[off:off + o * i].view(1, o, i).repeat(M, 1, 1)
+            b = init[off + o * i:off + o * i + o].view(1, o).repeat(M, 1)
+            params.append([W, b])
+            off += o * i + o
+        state = [[torch.zeros_like(t) for t in (W, b, W, b)] for W, b in params]   # mW, mb, vW, vb
+        step = 0
+        for e in range(E):
+            row = order[e]
+            row = row[fold[row] != f]
+            eloss = torch.zeros(M, dtype=dtype)
+            for b0 in range(0, n_train[f], bs):
+                idx = row[b0:b0 + bs]
+                B = idx.numel()
+                y = label[idx]
+                hs = forward(params, zz[:, idx])
+                dl = hs[-1][:, :, 1] - hs[-1][:, :, 0]
+                s = torch.where(y > 0, -dl, dl)
+                row_loss = s.clamp(min=0) + torch.log1p(torch.exp(-s.abs()))
+                eloss = eloss + row_loss.sum(1) / B * B
+                d1 = (torch.sigmoid(dl) - y) / B
+                delta = torch.stack([-d1, d1], 2)
+                lr_t, c2 = table[step, 0], table[step, 1]
+                grads = []
+                for l in range(L - 1, -1, -1):
+                    W, b = params[l]
+                    grads.append((delta.transpose(1, 2) @ hs[l], delta.sum(1)))
+                    if l > 0:
+                        delta = (delta @ W) * (hs[l] > 0).to(dtype)
+                grads.reverse()
+                for l in range(L):
+                    for j in range(2):
+                        w, g = params[l][j], grads[l][j] + wd * params[l][j]
+                        mom = b1 * state[l][j] + omb1 * g
+                        var = b2 * state[l][2 + j] + omb2 * g * g
+                        state[l][j], state[l][2 + j] = mom, var
+                        params[l][j] = w - lr_t * (mom / (var.sqrt() * c2 + eps))
+                step += 1
+            loss[:, f, e] = eloss / n_train[f]
+        held = torch.nonzero(fold == f).reshape(-1)
+        logits = forward(params, zz[:, held])[-1]
+        dl = logits[:, :, 1] - logits[:, :, 0]
+        prob[:, held] = torch.sigmoid(dl)
+        correct[:, f] = ((logits[:, :, 1] > logits[:, :, 0]) == (label[held] > 0)).sum(1).to(torch.int32)
+    bad = (~finite).to(torch.int32)
+    bad = torch.where(finite & ~torch.isfinite(loss).all(2).all(1), torch.full_like(bad, 2), bad)
+    nf = ~finite
+    correct[nf], loss[nf], prob[nf] = 0, 0, 0
+    return correct, loss, prob, bad
+
+
+@dataclass
+class ClassifierTestResult:
+    """Classifier two-sample test per observation (:func:`c2st_batched`), on the device of the
+    draws.  ``c2st`` [M] float64 is the reference's number: the mean over folds of each fold's
+    held-out accuracy (not the pooled accuracy); 0.5 = the classifier cannot tell the sets apart.
+    ``fold_accuracy`` [M, F] float64 and ``train_loss`` [M, F, E] float32 (the mean training loss of
+    each epoch) are per fold; ``probs`` [M, n + m] (None unless asked for) is each point's
+    probability of belonging to the second set under the classifier that held it out; ``fold`` [n +
+    m] uint8 (CPU) the fold of every pooled point.  An observation with a non-finite draw, or whose
+    training loss stopped being finite, is NaN throughout."""
+
+    c2st: Tensor
+    fold_accuracy: Tensor
+    train_loss: Tensor
+    probs: Optional[Tensor]
+    fold: Tensor
+    n: int
+    m: int
+    model: str
+    seed: int
+
+
+def c2st_batched(a, b, seed: int = 1, n_folds: int = 5, model: str = "mlp", z_score: bool = True, epochs: int = 100,
+                 batch_size: int = 128, lr: float = 1e-3, weight_decay: float = 0.0, return_probs: bool = False,
+                 engine=None) -> ClassifierTestResult:
+    """Classifier two-sample test between ``a`` [M, n, d] and ``b`` [M, m, d], observation by
+    observation (2-D inputs: M = 1; n != m allowed): the reference's
+    ``classifier_two_samples_test_torch`` (scripts/evaluate_ropefm.py:119-280) with its defaults.
+
+    Both sets are z-scored by ``a``'s per-observation mean and unbiased std (``z_score``; a zero
+    std counts as 1), pooled with labels 0 / 1, and split into ``n_folds`` stratified shuffled folds
+    (:func:`c2st_folds`, shared by all observations).  Per fold a fresh ``model`` ("mlp": d -> 4d ->
+    8d -> 8d -> 4d -> 2 with ReLUs, "mlp_small": d -> 4d -> 4d -> 2, "linear": d -> 2), started from
+    :func:`c2st_init`, is trained with Adam (``lr``, ``weight_decay``) for ``epochs`` passes in
+    batches of ``batch_size`` (:func:`c2st_order`) on cross-entropy and scored on the held-out fold;
+    ``c2st`` is the mean held-out accuracy over the folds.  ``seed`` fixes folds, order and init
+    through CPU generators, so a seed gives the same inputs on every machine.
+
+    Tensors on the GPU go through ``npfn_c2st_fit`` (``engine.c2st_fit`` when an engine is given,
+    otherwise the library's engine-free entry): one workgroup per (observation, fold) trains and
+    scores its classifier in a single launch.  It holds at most 16384 parameters in layers of at
+    most 128 units: "mlp" reaches d = 11, "mlp_small" d = 28, "linear" d = 64 (ValueError past
+    that); n + m <= 32768.  CPU tensors go through :func:`c2st_fit_host` in float32, the same
+    statement in torch.  Not offered: the reference's ``noise_scale``, ``cv="KFold"``, callable
+    models and scorings other than accuracy."""
+    a, b = torch.as_tensor(a).detach(), torch.as_tensor(b).detach()
+    if model not in C2ST_MODELS:
+        raise ValueError(f"c2st_batched: model must be one of {C2ST_MODELS}, got {model!r}")
+    if a.ndim == 2 and b.ndim == 2:
+        a, b = a[None], b[None]
+    if a.ndim != 3 or b.ndim != 3 or a.shape[0] != b.shape[0] or a.shape[2] != b.shape[2]:
+        raise ValueError(f"c2st_batched: a {tuple(a.shape)} and b {tuple(b.shape)} are not [M, n, d] and [M, m, d] "
+                         "(or [n, d] and [m, d])")
+    M, n, d = a.shape
+    m = b.shape[1]
+    if z_score and n < 2:
+        raise ValueError("c2st_batched: z_score needs n >= 2 draws in a (the unbiased std)")
+    F, E = int(n_folds), int(epochs)
+    fold = c2st_folds(n, m, F, seed)
+    widths = c2st_widths(model, d)
+    dev = a.device
+    a, b = a.to(torch.float32), b.to(device=dev, dtype=torch.float32)
+    z = torch.cat([a, b], 1)
+    check_c2st_args(z.shape, n, widths, F, E, batch_size)
+    if z_score:
+        z = _standardise(z, a)
+    order = c2st_order(n + m, E, seed)
+    init = c2st_init(widths, seed)
+    if dev.type == "cuda":
+        from .engine import c2st_fit
+
+        fit = engine.c2st_fit if engine is not None else c2st_fit
+        correct, loss, prob, _, bad = fit(z, n, fold, order, widths, init, E, batch_size, lr, weight_decay,
+                                          return_probs=return_probs)
+    else:
+        correct, loss, prob, bad = c2st_fit_host(z, n, fold, order, widths, init, E, batch_size, lr, weight_decay,
+                                                 dtype=torch.float32)
+        prob = prob if return_probs else None
+    correct, loss, bad = correct.to(dev), loss.to(dev), bad.to(dev)
+    held = torch.bincount(fold.to(torch.int64), minlength=F).to(device=dev, dtype=torch.float64)
+    acc = correct.to(torch.float64) / held[None, :]
+    nan = bad != 0
+    acc = torch.where(nan[:, None], torch.full_like(acc, float("nan")), acc)
+    loss = torch.where(nan[:, None, None], torch.full_like(loss, float("nan")), loss)
+    if prob is not None:
+        prob = prob.to(dev)
+        prob = torch.where(nan[:, None], torch.full_like(prob, float("nan")), prob)
+    return ClassifierTestResult(acc.mean(1), acc, loss, prob, fold, n, m, model, int(seed))

@@ -114,6 +114,9 @@ SIGNATURES = {
                                      ctypes.POINTER(_i32), _vp]),
     "npfn_w2_assign": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, ctypes.POINTER(_i32), _vp, _vp, _vp,
                                       ctypes.POINTER(_i32), _vp]),
+    "npfn_c2st_fit": (ctypes.c_int, [_vp, _i64, _i32, _i32, _i32, ctypes.POINTER(_i32), _i32, _vp, _vp, _i32,
+                                     ctypes.POINTER(_i32), ctypes.POINTER(_i32), _i32, _i32, _i32, _vp, _f, _f, _f, _f,
+                                     ctypes.POINTER(_i32), _vp, _vp, _vp, ctypes.POINTER(_i32), _vp]),
     "npfn_filter_stdeuclid": (ctypes.c_int, [_vp, _i64, _i32, _vp, _i64, _vp, _vp]),
     "npfn_sir_select": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _u64, _u64, _i64, _vp, _i32, _vp, _vp, _vp, _vp]),
     "npfn_kmeans_fit": (ctypes.c_int, [_vp, _i64, _i32, _i32, _u64, _i32, _f, _vp, _vp, _vp, _vp, _vp]),
@@ -306,6 +309,106 @@ def w2_assign(a, b, scale, lib=None):
         _check(lib, lib.npfn_w2_assign(_ptr(a), _ptr(b), n_obs, n, dim, _ptr(scale), i32p(assign), _ptr(duals),
                                        _ptr(cost_sum), _ptr(steps), i32p(bad), stream), "npfn_w2_assign")
     return assign, duals, cost_sum, steps, bad
+
+
+# npfn_c2st_fit's caps: a workgroup holds 16384 parameters in layers of at most 128 units
+C2ST_MAX_DIM, C2ST_MAX_POOL, C2ST_MAX_LAYERS, C2ST_MAX_WIDTH, C2ST_MAX_PARAMS = 64, 32768, 5, 128, 16384
+C2ST_MAX_FOLDS, C2ST_MAX_BATCH = 16, 4096
+C2ST_BETAS, C2ST_EPS = (0.9, 0.999), 1e-8   # torch.optim.Adam's defaults
+
+
+def c2st_param_count(widths) -> int:
+    """Parameters of the MLP with these layer widths: sum of out * (in + 1)."""
+    return sum(int(o) * (int(i) + 1) for i, o in zip(widths[:-1], widths[1:]))
+
+
+def check_c2st_args(z_shape, n_first, widths, n_folds, epochs, batch_size) -> Tuple[int, int, int, int]:
+    """(n_obs, n_pool, dim, P) of a c2st_fit call on ``z`` [n_obs, n_pool, dim]; ValueError for
+    whatever npfn_c2st_fit would refuse.  Pure host logic, shared by :func:`c2st_fit` and
+    :func:`npe_pfn.diagnostics.c2st_fit_host`."""
+    z_shape = tuple(z_shape)
+    if len(z_shape) != 3 or not 1 <= z_shape[2] <= C2ST_MAX_DIM:
+        raise ValueError(f"c2st_fit: z {z_shape} is not [n_obs, n_pool, 1 <= dim <= {C2ST_MAX_DIM}]")
+    n_obs, n_pool, dim = z_shape
+    if not 2 <= n_pool <= C2ST_MAX_POOL or not 1 <= int(n_first) <= n_pool - 1:
+        raise ValueError(f"c2st_fit: need 2 <= n_pool <= {C2ST_MAX_POOL} and 1 <= n_first <= n_pool - 1, got "
+                         f"{n_pool} and {n_first}")
+    widths = [int(w) for w in widths]
+    if not 1 <= len(widths) - 1 <= C2ST_MAX_LAYERS or widths[0] != dim or widths[-1] != 2 \
+            or not all(1 <= w <= C2ST_MAX_WIDTH for w in widths):
+        raise ValueError(f"c2st_fit: widths {widths} are not 1..{C2ST_MAX_LAYERS} layers from dim = {dim} to 2 "
+                         f"logits with every width in 1..{C2ST_MAX_WIDTH}")
+    P = c2st_param_count(widths)
+    if P > C2ST_MAX_PARAMS:
+        raise ValueError(f"c2st_fit: widths {widths} have {P} parameters, above the {C2ST_MAX_PARAMS} that one "
+                         "workgroup holds ('mlp' reaches dim 11, 'mlp_small' dim 28, 'linear' dim 64)")
+    if not 2 <= int(n_folds) <= C2ST_MAX_FOLDS or int(epochs) < 1:
+        raise ValueError(f"c2st_fit: need 2 <= n_folds <= {C2ST_MAX_FOLDS} and epochs >= 1, got {n_folds} and {epochs}")
+    if not 1 <= int(batch_size) <= C2ST_MAX_BATCH:
+        raise ValueError(f"c2st_fit: batch_size must lie in 1..{C2ST_MAX_BATCH}, got {batch_size}")
+    return n_obs, n_pool, dim, P
+
+
+def c2st_fit(z, n_first, fold, order, widths, init, epochs, batch_size=128, lr=1e-3, weight_decay=0.0,
+             return_probs=True, return_params=False, lib=None):
+    """npfn_c2st_fit on the GPU that holds ``z`` (needs no engine): ``(correct [n_obs, n_folds]
+    int32, loss [n_obs, n_folds, epochs], prob [n_obs, n_pool] or None, params [n_obs, n_folds, P]
+    or None, bad [n_obs] int32)`` on that device, on its current stream.  ``z`` [n_obs, n_pool, dim]
+    is every observation's pooled sample (label 0 for the first ``n_first`` points), ``fold``
+    [n_pool] the fold that holds each point out (:func:`npe_pfn.diagnostics.c2st_folds`), ``order``
+    [epochs, n_pool] one permutation per epoch (:func:`npe_pfn.diagnostics.c2st_order`), ``widths``
+    and ``init`` the network and its start (``c2st_widths``, ``c2st_init``).  Here ``order`` is
+    compacted per fold (a stable boolean mask on the device drops the fold's own points), so the
+    kernel trains on consecutive runs of ``batch_size`` entries.  The definition of every number:
+    :func:`npe_pfn.diagnostics.c2st_fit_host`.  At most 16384 parameters in layers of at most 128
+    units.  ValueError for arguments that do not fit, before the C call."""
+    from .diagnostics import c2st_adam_table
+
+    z = torch.as_tensor(z)
+    if z.device.type != "cuda":
+        raise ValueError("c2st_fit: z must live on the GPU (npe_pfn.diagnostics.c2st_fit_host is the CPU statement)")
+    z = z.to(torch.float32).contiguous()
+    fold_cpu = torch.as_tensor(fold).detach().cpu().to(torch.int64)
+    n_folds = int(fold_cpu.max()) + 1 if fold_cpu.numel() else 0
+    epochs, batch_size = int(epochs), int(batch_size)
+    n_obs, n_pool, dim, P = check_c2st_args(z.shape, n_first, widths, n_folds, epochs, batch_size)
+    order = torch.as_tensor(order)
+    init = torch.as_tensor(init)
+    if tuple(fold_cpu.shape) != (n_pool,) or tuple(order.shape) != (epochs, n_pool) or tuple(init.shape) != (P,):
+        raise ValueError(f"c2st_fit: fold {tuple(fold_cpu.shape)}, order {tuple(order.shape)} and init "
+                         f"{tuple(init.shape)} are not [{n_pool}], [{epochs}, {n_pool}] and [{P}]")
+    held = torch.bincount(fold_cpu, minlength=n_folds)
+    n_train = [n_pool - int(h) for h in held]
+    if min(n_train) < 1:
+        raise ValueError("c2st_fit: a fold holds every point out")
+    dev = z.device
+    fold_d = fold_cpu.to(device=dev, dtype=torch.uint8).contiguous()
+    order_d = order.to(device=dev, dtype=torch.int64).clamp(0, n_pool - 1)
+    order_ld = max(n_train)
+    packed = torch.zeros((n_folds, epochs, order_ld), dtype=torch.int32, device=dev)
+    of = fold_d[order_d]
+    for f in range(n_folds):
+        packed[f, :, :n_train[f]] = order_d[of != f].view(epochs, n_train[f]).to(torch.int32)
+    n_steps = epochs * ((order_ld + batch_size - 1) // batch_size)
+    adam = c2st_adam_table(lr, n_steps).to(dev).contiguous()
+    init_d = init.to(device=dev, dtype=torch.float32).contiguous()
+    correct = torch.empty((n_obs, n_folds), dtype=torch.int32, device=dev)
+    loss = torch.empty((n_obs, n_folds, epochs), dtype=torch.float32, device=dev)
+    prob = torch.empty((n_obs, n_pool), dtype=torch.float32, device=dev) if return_probs else None
+    params = torch.empty((n_obs, n_folds, P), dtype=torch.float32, device=dev) if return_params else None
+    bad = torch.empty((n_obs,), dtype=torch.int32, device=dev)
+    lib = lib or load_library()
+    host_w = (_i32 * len(widths))(*[int(w) for w in widths])
+    host_nt = (_i32 * n_folds)(*n_train)
+    i32p = lambda t: ctypes.cast(ctypes.c_void_p(t.data_ptr()), ctypes.POINTER(_i32))  # noqa: E731
+    with torch.cuda.device(dev):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _check(lib, lib.npfn_c2st_fit(_ptr(z), n_obs, n_pool, int(n_first), dim, host_w, len(widths) - 1, _ptr(init_d),
+                                      _ptr(fold_d), n_folds, i32p(packed), host_nt, order_ld, epochs, batch_size,
+                                      _ptr(adam), C2ST_BETAS[0], C2ST_BETAS[1], C2ST_EPS, float(weight_decay),
+                                      i32p(correct), _ptr(loss), _ptr(prob), _ptr(params), i32p(bad), stream),
+               "npfn_c2st_fit")
+    return correct, loss, prob, params, bad
 
 
 MIX_OPS = {"log": 0, "prob": 1, "sample": 2, "nll": 3, "score": 4,   # npfn.h NPFN_MIX_*
@@ -984,6 +1087,15 @@ class Engine:
         a, b = torch.as_tensor(a), torch.as_tensor(b)
         check_transport_args(a.shape, b.shape)
         return w2_assign(a.to(self.device), b.to(self.device), torch.as_tensor(scale).to(self.device), lib=self.lib)
+
+    # ------------------------------------------------- classifier two-sample test (npfn_c2st.hip)
+    def c2st_fit(self, z, n_first, fold, order, widths, init, epochs, batch_size=128, lr=1e-3, weight_decay=0.0,
+                 return_probs=True, return_params=False):
+        """npfn_c2st_fit on the engine's device and stream: :func:`c2st_fit` of this module (the
+        call needs no engine state; this method only supplies the device and the library)."""
+        z = torch.as_tensor(z)
+        return c2st_fit(z.to(self.device), n_first, fold, order, widths, init, epochs, batch_size, lr, weight_decay,
+                        return_probs, return_params, lib=self.lib)
 
     def filter_stdeuclid(self, x: torch.Tensor, obs: torch.Tensor, k: int) -> torch.Tensor:
         x = _dev_f32(x, self.device)

@@ -29,8 +29,8 @@ from torch import Tensor
 from torch.distributions import Distribution
 
 from .accept_reject_sampler import accept_reject_sample
-from .diagnostics import (CoverageRanks, TransportResult, TwoSampleResult, bar_cdf, mmd_batched, rank_accumulate_host,
-                          wasserstein_batched)
+from .diagnostics import (ClassifierTestResult, CoverageRanks, TransportResult, TwoSampleResult, bar_cdf, c2st_batched,
+                          mmd_batched, rank_accumulate_host, wasserstein_batched)
 from .kmeans import KMeansState
 from .marginals import PosteriorMarginals
 from .pair_marginals import MAX_PER as PAIR_MAX_PER
@@ -589,6 +589,29 @@ class NPE_PFN_Core:
         draws = self.sample_batched(x, (T,))
         engine = self._model.engine if self._fused() and draws.device.type == "cuda" else None
         return wasserstein_batched(draws, theta_ref.to(draws.device), engine=engine, **kw)
+
+    def c2st_batched(self, theta_ref: Tensor, x: Tensor, num_posterior_samples: Optional[int] = None,
+                     **kw) -> ClassifierTestResult:
+        """Classifier two-sample test of this estimator's draws against reference draws,
+        observation by observation: ``theta_ref`` [M, T, d_theta] are the reference draws for ``x``
+        [M, dx].  Draws ``num_posterior_samples`` (default T) per observation with
+        :meth:`sample_batched` -- the sample counter advances as that call advances it -- and
+        returns :func:`npe_pfn.diagnostics.c2st_batched` ``(draws, theta_ref, **kw)``: ``seed``,
+        ``n_folds``, ``model``, ``z_score``, ``epochs``, ``batch_size``, ``lr``, ``weight_decay`` and
+        ``return_probs`` are its arguments.  The draws are the first set, as in the reference
+        harness, so they set the z-score."""
+        theta_ref = torch.as_tensor(theta_ref)
+        n_obs = 1 if torch.as_tensor(x).ndim < 2 else x.shape[0]
+        dth = self._theta_train.shape[1]
+        if theta_ref.ndim != 3 or theta_ref.shape[0] != n_obs or theta_ref.shape[1] < 1 or theta_ref.shape[2] != dth:
+            raise ValueError(f"c2st_batched: theta_ref {tuple(theta_ref.shape)} is not [{n_obs}, T >= 1, {dth}] (the "
+                             "reference draws of every row of x)")
+        n = theta_ref.shape[1] if num_posterior_samples is None else int(num_posterior_samples)
+        if n < 1:
+            raise ValueError(f"c2st_batched: num_posterior_samples ({n}) must be >= 1")
+        draws = self.sample_batched(x, (n,))
+        engine = self._model.engine if self._fused() and draws.device.type == "cuda" else None
+        return c2st_batched(draws, theta_ref.to(draws.device), engine=engine, **kw)
 
     def pit_batched(self, theta: Tensor, x: Tensor) -> Tensor:
         """Per-dimension probability integral transform u_k = F_k(theta_k | x, theta_<k) of the
@@ -1178,6 +1201,12 @@ class TabPFN_Based_Uncond_Estimator(NPE_PFN_Core):
         :meth:`sample` with :func:`npe_pfn.diagnostics.wasserstein_batched`."""
         raise NotImplementedError("TabPFN_Based_Uncond_Estimator has no observations to batch over (its x is a "
                                   "dummy column); call npe_pfn.diagnostics.wasserstein_batched on sample()'s draws")
+
+    def c2st_batched(self, theta_ref: Tensor, x: Tensor = None, *args, **kwargs):
+        """Not provided, for the reason given at :meth:`log_prob_batched`; compare draws of
+        :meth:`sample` with :func:`npe_pfn.diagnostics.c2st_batched`."""
+        raise NotImplementedError("TabPFN_Based_Uncond_Estimator has no observations to batch over (its x is a "
+                                  "dummy column); call npe_pfn.diagnostics.c2st_batched on sample()'s draws")
 
     def log_prob(self, theta: Tensor, x: Tensor = None, max_sampling_batch_size: int = 10_000,
                  mode: str = "autoregressive", eps: float = 1e-15, **ratio_kwargs) -> Tensor:
