@@ -350,12 +350,23 @@ int npfn_ar_score(npfn_engine* h, const float* x_ctx, const float* theta_ctx, in
                   float* logp_steps, float* cdf_steps, float eps, void* stream);
 
 /* K9: prior-support check of a box prior (npe_pfn.py:581-600 with
- * BoxUniform): mask[i] = all_j(low_j <= theta[i,j] <= high_j). */
+ * BoxUniform): mask[i] = all_j(low_j <= theta[i,j] <= high_j), 1 or 0.
+ * The bounds are closed: theta == low_j and theta == high_j are inside, the next float past
+ * either is outside; -0.0 equals +0.0.  Both comparisons are false for NaN, so a row with a
+ * NaN cell, or a column with a NaN bound, is outside.  Infinite bounds are allowed (+-inf
+ * cells are inside a bound of the same infinity); low_j > high_j accepts no row.
+ * n_rows == 0 launches nothing (theta and mask may then be NULL).
+ * Errors: NPFN_EINVAL for dim < 1, n_rows < 0 or a missing pointer with n_rows > 0. */
 int npfn_box_support(const float* theta, int64_t n_rows, int32_t dim, const float* low,
                      const float* high, uint8_t* mask, void* stream);
 
 /* K9/K10 stream compaction: rows of src [n_rows, dim] with mask != 0 are
- * written in order to dst; *count_out (device int64) receives the count. */
+ * written in order to dst; *count_out (device int64) receives the count.
+ * Any non-zero mask byte selects its row (not only 1).  dst [n_rows, dim] is written in rows
+ * [0, count) only: rows from count on keep what they held.  n_rows == 0 launches no kernel and
+ * sets *count_out = 0 (src, mask and dst may then be NULL, as the pointers of empty arrays are).
+ * Errors: NPFN_EINVAL for dim < 1, n_rows < 0, a missing count_out, or a missing src, mask or
+ * dst with n_rows > 0. */
 int npfn_compact_rows(const float* src, const uint8_t* mask, int64_t n_rows, int32_t dim,
                       float* dst, int64_t* count_out, void* stream);
 
@@ -625,7 +636,15 @@ int npfn_c2st_fit(const float* z, int64_t n_obs, int32_t n_pool, int32_t n_first
 
 /* K12 standardized-Euclidean context filter (support_posterior.py:357-369):
  * idx_out[0:k] = indices of the k rows of x [n_rows, dim] closest to obs in
- * z-scored Euclidean distance, ascending (ties by lower index). */
+ * z-scored Euclidean distance, ascending (ties by lower index).
+ * Column mean and unbiased std (n_rows - 1; n_rows itself for a single row) are fp64 sums of
+ * the fp32 values rounded to fp32; the distance is fp32.  Rows are ordered by (distance, row):
+ * equal distances keep their row order, and a NaN distance sorts after every number, again by
+ * row.  A constant column (std 0) or a NaN cell in a column makes every distance NaN, so the
+ * result is then rows 0 .. k-1.  k == 0 launches nothing (idx_out may then be NULL).
+ * Errors: NPFN_EINVAL for dim < 1, n_rows < 1, n_rows > 2^32 - 1, k < 0, k > n_rows, a missing
+ * x or obs, or a missing idx_out with k > 0; NPFN_ENOMEM when the sort keys (8 bytes per row,
+ * rounded up to a power of two) do not fit. */
 int npfn_filter_stdeuclid(const float* x, int64_t n_rows, int32_t dim, const float* obs, int64_t k,
                           int64_t* idx_out, void* stream);
 
@@ -636,7 +655,14 @@ int npfn_filter_stdeuclid(const float* x, int64_t n_rows, int32_t dim, const flo
  * lq < *thr; ess_out[g] = 1 / sum softmax(log_ratio)^2; pick_out[g] = inverse-CDF
  * index of softmax(log_ratio) at u = Philox4x32-10(counter=(group_offset + g,
  * counter), key=seed).  If theta_out != NULL, theta_out[g, :] = theta[g*k + pick, :]
- * (theta [n_groups * k, dim]). */
+ * (theta [n_groups * k, dim]).
+ * The truncation is strict: lq == *thr keeps its lpr.  A group whose ratios are all NaN has
+ * ess NaN and pick 0.  group_offset only shifts the Philox row: a call on groups [a, b) of the
+ * arrays with group_offset = a gives groups a .. b-1 of the unsplit call bit for bit.
+ * n_groups == 0 launches nothing (every array may then be NULL).
+ * Errors: NPFN_EINVAL for n_groups < 0, k < 1, group_offset < 0, more than 4 (2^31 - 1) groups, and with
+ * n_groups > 0 a missing lpr, lq, thr, pick_out or ess_out, or theta_out without theta or with
+ * dim < 1. */
 int npfn_sir_select(const float* lpr, const float* lq, const float* thr, int64_t n_groups, int32_t k,
                     uint64_t seed, uint64_t counter, int64_t group_offset, const float* theta,
                     int32_t dim, int64_t* pick_out, float* ess_out, float* theta_out, void* stream);
@@ -668,7 +694,8 @@ int npfn_kmeans_fit(const float* pts, int64_t n_rows, int32_t dim, int32_t k, ui
                     int64_t* n_iter, void* stream);
 /* K13 predict: labels[i] = argmin_c ||pts[i] - centers[c]||^2 (ties: lower c), fp64 distances
  * of the fp32 inputs (KMeans.predict, reference npe_pfn.py:855).  Asynchronous.  Same caps on
- * dim, k * dim and n_rows as npfn_kmeans_fit. */
+ * dim, k * dim and n_rows as npfn_kmeans_fit.  n_rows == 0 launches nothing (pts and labels
+ * may then be NULL). */
 int npfn_kmeans_assign(const float* pts, int64_t n_rows, int32_t dim, const float* centers, int32_t k,
                        int64_t* labels, void* stream);
 

@@ -379,10 +379,11 @@ int npfn_kmeans_fit(const float* pts, int64_t n_rows, int32_t dim, int32_t k, ui
 
 int npfn_kmeans_assign(const float* pts, int64_t n_rows, int32_t dim, const float* centers, int32_t k,
                        int64_t* labels, void* stream) {
-  if (!pts || !centers || !labels) return fail(NPFN_EINVAL, "kmeans_assign: null pointer");
   if (const int rc = check_shape("kmeans_assign", n_rows, dim, k)) return rc;
   if (n_rows < 0) return fail(NPFN_EINVAL, "kmeans_assign: need n_rows >= 0");
-  if (n_rows == 0) return NPFN_OK;
+  if (!centers) return fail(NPFN_EINVAL, "kmeans_assign: null pointer");
+  if (n_rows == 0) return NPFN_OK;  // empty pts / labels may come as null pointers: no launch
+  if (!pts || !labels) return fail(NPFN_EINVAL, "kmeans_assign: null pointer");
   launch_assign((hipStream_t)stream, assign_blocks(n_rows, k, dim), pts, n_rows, dim, k, nullptr, centers, nullptr,
                 labels, nullptr, nullptr);
   return launch_status("kmeans_assign: k_km_assign launch");

@@ -201,8 +201,14 @@ extern "C" {
 
 int npfn_compact_rows(const float* src, const uint8_t* mask, int64_t n_rows, int32_t dim, float* dst,
                       int64_t* count_out, void* stream) {
-  if (!src || !mask || !dst || !count_out) return fail(NPFN_EINVAL, "compact_rows: null pointer");
   if (dim < 1 || n_rows < 0) return fail(NPFN_EINVAL, "compact_rows: need dim >= 1 and n_rows >= 0");
+  if (!count_out) return fail(NPFN_EINVAL, "compact_rows: null pointer");
+  if (n_rows == 0) {  // empty arrays may come as null pointers: no launch, the count is 0
+    if (hipMemsetAsync(count_out, 0, sizeof(int64_t), (hipStream_t)stream) != hipSuccess)
+      return launch_status("compact_rows: zeroing the count");
+    return NPFN_OK;
+  }
+  if (!src || !mask || !dst) return fail(NPFN_EINVAL, "compact_rows: null pointer");
   hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, (hipStream_t)stream, src, mask, n_rows, dim, dst,
                      count_out);
   return launch_status("compact_rows: k_compact launch");
@@ -210,10 +216,12 @@ int npfn_compact_rows(const float* src, const uint8_t* mask, int64_t n_rows, int
 
 int npfn_filter_stdeuclid(const float* x, int64_t n_rows, int32_t dim, const float* obs, int64_t k,
                           int64_t* idx_out, void* stream) {
-  if (!x || !obs || !idx_out) return fail(NPFN_EINVAL, "filter_stdeuclid: null pointer");
   if (dim < 1 || n_rows < 1 || k < 0 || k > n_rows)
     return fail(NPFN_EINVAL, "filter_stdeuclid: need dim >= 1, n_rows >= 1 and 0 <= k <= n_rows");
   if (n_rows > 0xffffffffll) return fail(NPFN_EINVAL, "filter_stdeuclid: more than 2^32 rows");
+  if (!x || !obs) return fail(NPFN_EINVAL, "filter_stdeuclid: null pointer");
+  if (k == 0) return NPFN_OK;  // nothing to select: no launch, idx_out (empty) may be null
+  if (!idx_out) return fail(NPFN_EINVAL, "filter_stdeuclid: null pointer");
   hipStream_t s = (hipStream_t)stream;
   int64_t npow = 1;
   while (npow < n_rows) npow <<= 1;
@@ -234,7 +242,7 @@ int npfn_filter_stdeuclid(const float* x, int64_t n_rows, int32_t dim, const flo
   for (int64_t kk = 2; kk <= npow; kk <<= 1)
     for (int64_t j = kk >> 1; j > 0; j >>= 1)
       hipLaunchKernelGGL(k_bitonic_step, dim3(nb), dim3(256), 0, s, keys, npow, kk, j);
-  if (k > 0) hipLaunchKernelGGL(k_take_idx, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, s, keys, k, idx_out);
+  hipLaunchKernelGGL(k_take_idx, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, s, keys, k, idx_out);
   (void)hipFreeAsync(keys, s);
   (void)hipFreeAsync(ms, s);
   return launch_status("filter_stdeuclid: kernel launch");
@@ -243,11 +251,11 @@ int npfn_filter_stdeuclid(const float* x, int64_t n_rows, int32_t dim, const flo
 int npfn_sir_select(const float* lpr, const float* lq, const float* thr, int64_t n_groups, int32_t k,
                     uint64_t seed, uint64_t counter, int64_t group_offset, const float* theta, int32_t dim,
                     int64_t* pick_out, float* ess_out, float* theta_out, void* stream) {
-  if (!lpr || !lq || !thr || !pick_out || !ess_out) return fail(NPFN_EINVAL, "sir_select: null pointer");
   if (n_groups < 0 || k < 1 || group_offset < 0)
     return fail(NPFN_EINVAL, "sir_select: need n_groups >= 0, k >= 1 and group_offset >= 0");
+  if (n_groups == 0) return NPFN_OK;  // empty arrays may come as null pointers: no launch
+  if (!lpr || !lq || !thr || !pick_out || !ess_out) return fail(NPFN_EINVAL, "sir_select: null pointer");
   if (theta_out && (!theta || dim < 1)) return fail(NPFN_EINVAL, "sir_select: theta_out needs theta and dim >= 1");
-  if (n_groups == 0) return NPFN_OK;
   if ((n_groups + 3) / 4 > 0x7fffffffll) return fail(NPFN_EINVAL, "sir_select: too many groups for one launch");
   hipLaunchKernelGGL(k_sir_select, dim3((unsigned)((n_groups + 3) / 4)), dim3(256), 0, (hipStream_t)stream, lpr,
                      lq, thr, n_groups, (int)k, seed, counter, group_offset, theta, theta_out ? (int)dim : 0,

@@ -71,6 +71,31 @@ def fit(pts: np.ndarray, k: int, seed: int, max_iter: int = 300, tol: float = 1e
     return centers, labels, counts, n_iter
 
 
+# Degenerate inputs shared by tests/test_support_ref_host.py (which pins what `fit` gives on
+# them) and tests/test_gpu_kmeans.py (which holds the device to it).  Every coordinate is a small
+# integer, so every member sum is exact in any order and the centres must agree bit for bit.
+FIVE_ROWS = np.array([[0, 0, 0], [4, 1, 0], [1, 5, 2], [7, 7, 7], [2, 8, 3]], dtype=np.float32)
+LATTICE_SHAPES = [(129, 4), (64, 2), (1000, 7)]
+
+
+def few_distinct_points() -> np.ndarray:
+    """5 distinct rows tiled 40x: fewer distinct points than the k = 8 asked for."""
+    return np.tile(FIVE_ROWS, (40, 1))
+
+
+def identical_points() -> np.ndarray:
+    return np.full((100, 3), 2.0, dtype=np.float32)
+
+
+def lattice_points(n: int) -> np.ndarray:
+    return (np.arange(n) % 17).astype(np.float32)[:, None]
+
+
+def symmetric_points() -> np.ndarray:
+    """{-1, 0, 1} x 50 in one dimension: 0 is exactly midway between centres at -1 and 1."""
+    return np.tile(np.array([-1.0, 0.0, 1.0], dtype=np.float32), 50)[:, None]
+
+
 class KMeansShim:
     """The part of sklearn.cluster.KMeans the reference's unconditional estimator uses
     (``fit``, ``labels_``, ``predict``), over this module (tests/golden/make_golden_uncond.py)."""
