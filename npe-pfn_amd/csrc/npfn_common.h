@@ -223,6 +223,17 @@ __device__ __forceinline__ float gelu_fast(float x) {
   return x * (x >= 0.f ? 1.0f - h : h);
 }
 
+// Encoder, one feature of a token (k_encode; k_row_layer's layer-0 launch): from the token's seed
+// a0..a3 (encode_seed, npfn_kernels.hip), the feature's weights w (encw[d][0..3]; the target token:
+// yencw[d][0..1]) and positional value pw (pos[c][d]).
+// explicit fma order: w0 a0 + w1 a1 + w2 a2 + w3 a3 + pos as the contracted expression
+// evaluates (the first product fused onto the rounded second)
+__device__ __forceinline__ float encode_expand(bool target, float w0, float w1, float w2, float w3, float pw,
+                                               float a0, float a1, float a2, float a3) {
+  const float s01 = __fmaf_rn(w0, a0, w1 * a1);
+  return target ? s01 : __fmaf_rn(w3, a3, __fmaf_rn(w2, a2, s01)) + pw;
+}
+
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 
 // gelu_fast on two values: the polynomial and products run as packed fp32

@@ -155,6 +155,7 @@ struct FitSet {
 // Forward workspaces of one stream (token tensors of the rows in flight).
 struct Work {
   DevBuf resid, resid_bf, qkv, attn, hid;
+  DevBuf seed;  // [tok][4] encoder seeds of the fused path's layer-0 launch
   void release();
 };
 
@@ -236,6 +237,9 @@ struct npfn_engine {
   // i < ne, of cfg.n_estimators; a partial set is the estimator-parallel multi-GPU split
   int e0 = 0, ne = 0, es = 1;
   bool fused = true;  // k_row_layer path (NPFN_UNFUSED=1 selects the per-sublayer kernels)
+  // the fused path's layer-0 launch expands the tokens from k_encode_seed's seeds
+  // (NPFN_ENC_FUSED=0: k_encode writes them and the launch reads them back)
+  bool enc_fused = true;
   // dynamic row-kernel tile schedule (RowLayerParams::tile_ctr): one device counter per stream
   // the row kernel runs on (the caller's, side_t), the host keeps each counter's running base
   static constexpr int kTileCtrs = 8;
@@ -329,7 +333,7 @@ void free_buf(DevBuf& b) {
 }  // namespace
 
 void Work::release() {
-  DevBuf* bufs[] = {&resid, &resid_bf, &qkv, &attn, &hid};
+  DevBuf* bufs[] = {&resid, &resid_bf, &qkv, &attn, &hid, &seed};
   for (DevBuf* b : bufs) free_buf(*b);
 }
 
@@ -697,11 +701,22 @@ int forward_groups_fused(npfn_engine* h, const Fit::Group* gs, int ng, const flo
   bf16_t* qkv = (bf16_t*)wk.qkv.p;
   bf16_t* attn = (bf16_t*)wk.attn.p;
   if (!train && !tgt) return fail(NPFN_EINVAL, "forward: the test side needs the target-token buffer");
+  // the encoder: 16-byte seeds that the layer-0 launch expands in registers, or (rows of more
+  // than 64 tokens in the batch -- the long-row kernel instances -- or NPFN_ENC_FUSED=0) the
+  // tokens themselves into resid.  Bit for bit the same tokens either way.
+  bool encf = h->enc_fused;
+  for (int g = 0; g < ng; ++g) encf = encf && gs[g].C <= 64;
+  float* seed = nullptr;
+  if (encf) {
+    RCHK(ensure(wk.seed, tokens * 4 * sizeof(float), s));
+    seed = (float*)wk.seed.p;
+  }
   for (int g = 0; g < ng; ++g) {
     const int64_t tg = (int64_t)gs[g].ne * rows * gs[g].C;
     const DevFit fp = h->devfit(gs[g], train);
-    ProfGuard pg(h, P_ENCODE, 0.0, (double)tg * 192 * 4, s);
-    launch_encode(ytr, ldy, rows, fp, h->encw, h->yencw, h->pos, resid + tok0[g] * 192, nullptr, s);
+    ProfGuard pg(h, P_ENCODE, 0.0, (double)tg * (encf ? 16 : 192 * 4), s);
+    if (encf) launch_encode_seed(ytr, ldy, rows, fp, seed + tok0[g] * 4, s);
+    else launch_encode(ytr, ldy, rows, fp, h->encw, h->yencw, h->pos, resid + tok0[g] * 192, nullptr, s);
   }
   const double n_keys = (double)h->f->n;
   const int nproj = train ? 3 : 1;
@@ -727,7 +742,14 @@ int forward_groups_fused(npfn_engine* h, const Fit::Group* gs, int ng, const flo
     sg.tmem = gs[g].C;
     sg.tofs = 0;
     sg.tstride = 1;
+    sg.seed = encf ? seed + tok0[g] * 4 : nullptr;
+    sg.G = gs[g].C - 1;
     rp.ntiles += (rows + sg.rpt - 1) / sg.rpt * gs[g].ne;
+  }
+  if (encf) {
+    rp.encw = h->encw;
+    rp.yencw = h->yencw;
+    rp.pos = h->pos;
   }
   rp.dff = dff;
   rp.out_qkv = train ? 1 : 0;
@@ -781,6 +803,7 @@ int forward_groups_fused(npfn_engine* h, const Fit::Group* gs, int ng, const flo
     ProfGuard pg(h, P_ROW_LAYER, pre_flops_sum, (double)tokens * (192 * 8 + nproj * 384), s);
     RCHK(row_launch(h, rp, s));
   }
+  rp.encw = rp.yencw = rp.pos = nullptr;  // the later launches read resid
   for (int l = 0; l < L; ++l) {
     for (int g = 0; g < ng; ++g) {
       const size_t kv_layer = (size_t)gs[g].ne * gs[g].C * 6 * h->f->ntile * 2048;
@@ -1843,6 +1866,8 @@ int npfn_engine_create(const npfn_config* cfg, const float* weights, size_t n_we
     // NPFN_UNFUSED=1 / =0 forces the per-sublayer / fused path; unset = default
     const char* env = getenv("NPFN_UNFUSED");
     h->fused = env ? (env[0] != '1') : kFusedDefault;
+    const char* ef = getenv("NPFN_ENC_FUSED");  // 0: k_encode + the layer-0 launch's residual load
+    h->enc_fused = !(ef && ef[0] == '0');
     const char* dt = getenv("NPFN_ROWK_STATIC");
     h->dyn_tiles = !(dt && dt[0] == '1');
     const char* cr = getenv("NPFN_CHUNK_ROWS");  // A/B: query rows per forward chunk (npfn_set_chunk_rows)

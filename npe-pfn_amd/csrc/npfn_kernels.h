@@ -116,6 +116,10 @@ struct RowSeg {
   // runs the rows' target tokens alone (C = 1; tmem = tstride = the rows' token count,
   // tofs = that count - 1): the decoder reads nothing else of the last layer.
   int tmem, tofs, tstride;
+  // layer-0 entry with the encoder fused in (RowLayerParams::encw): the tokens' seeds
+  // [tok][4] (k_encode_seed) and the target column; the launch expands them instead of reading resid
+  const float* seed;
+  int G;
 };
 // NPFN_GELU_F16: the row kernel's MLP hidden slabs go to W2 as fp16 B fragments from a packed-f16
 // GELU (v_pk_*_f16), and the W2 chunk images of the weight stream are fp16 (v_mfma_f32_16x16x32_f16);
@@ -142,6 +146,10 @@ struct RowLayerParams {
   int stream_chunks;
   const float *ln2g, *ln2b, *ln3g, *ln3b;
   const float *ln1g, *ln1b;
+  // encoder tables (encw [192][4], yencw [192][2], pos [.][192]) of a layer-0 entry launch
+  // (do_post = 0) that expands RowSeg::seed; encw = nullptr: the launch reads the encoded resid.
+  // Rows of at most 64 tokens only (the long-row instances keep k_encode).
+  const float *encw, *yencw, *pos;
   // dynamic tile schedule (npfn_rowk2.hip): a workgroup takes its next tile from a per-stream
   // device counter, tile = atomicAdd(tile_ctr, 1) - tile_base; the counter only grows (every
   // launch advances it by ntiles + grid: each workgroup's last fetch overshoots once).
@@ -217,6 +225,8 @@ void launch_target_tf(const float* y, int64_t ldy, int64_t n, const float* bz, i
                       TransEntry* tab, uint8_t* tcancel, float* pscratch, hipStream_t s, bool fit_lambda = true);
 void launch_encode(const float* ytr, int64_t ldy, int64_t R, const DevFit& fp, const float* encw,
                    const float* yencw, const float* pos, float* resid, bf16_t* resid_bf, hipStream_t s);
+// the tokens' seeds alone: seed [E][R][C][4] (a0..a3 of encode_seed), for k_row_layer's fused encoder
+void launch_encode_seed(const float* ytr, int64_t ldy, int64_t R, const DevFit& fp, float* seed, hipStream_t s);
 void launch_gemm(int epi, const bf16_t* A, int64_t lda, const bf16_t* W, int64_t M, int N, int K,
                  const EpiParams& p, hipStream_t s);
 void launch_feat_attn(const bf16_t* qkv, bf16_t* out, int64_t rows, int C, hipStream_t s);

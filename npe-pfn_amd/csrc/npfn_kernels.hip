@@ -1503,54 +1503,22 @@ __global__ __launch_bounds__(256) void k_target_tf(const float* __restrict__ y, 
 // ================================================================ K1 encoder
 // tokens [E][R][C][d]: resid fp32 + bf16 copy.  One wave per token; features come from the
 // views table through the estimator's shuffled column list (k_build_params).
+// The fused path with rows of at most 64 tokens runs k_encode_seed instead (encode_seed alone, 16 B
+// per token) and k_row_layer's layer-0 launch applies encode_expand in registers (npfn_rowk2.hip).
 // U32: the launch's tokens < 2^32, so (estimator, row, token) come from FastDiv (the 64-bit
 // divisions bound the kernel: r04 ran it at ~2 TB/s of stores); else 64-bit division.
 #ifndef NPFN_ENC_SPEC  // 1: feature loads ahead of Fe (r05: k_encode 3.53 -> 3.37 ms, bitwise equal,
 #define NPFN_ENC_SPEC 1  // profiles/r05/ab_encode_spec_r05bd.txt); 0: loads behind the j < Fe test
 #endif
-template <bool U32>
-__device__ __forceinline__ void encode_token(int64_t tok, const float* __restrict__ ytr, int64_t ldy, int64_t R,
-                                             const DevFit& fp, const float* __restrict__ encw,
-                                             const float* __restrict__ yencw, const float* __restrict__ pos,
-                                             float* __restrict__ resid, bf16_t* __restrict__ resid_bf,
-                                             const FastDiv& divC, const FastDiv& divR) {
-  const int lane = threadIdx.x & 63;
-  const int C = fp.C;
-  int c, ei;
-  int64_t r;
-  if constexpr (U32) {  // tok is wave-uniform: the decomposition runs once per wave
-    uint32_t cu, ru;
-    const uint32_t rr = divC.divmod((uint32_t)tok, cu);
-    ei = (int)divR.divmod(rr, ru);
-    c = (int)cu;
-    r = ru;
-  } else {
-    c = (int)(tok % C);
-    const int64_t rr = tok / C;
-    r = rr % R;
-    ei = (int)(rr / R);
-  }
+// encode_seed: everything of a token up to the four scalars a0..a3 that decide its 192 values
+// (view gather, NaN / +-inf indicators, clamping, group scale; the target / classifier branches).
+// (c, r, ei): the token's column, row and estimator of the group -- wave-uniform in k_encode,
+// per lane in k_encode_seed.
+__device__ __forceinline__ float4 encode_seed(const float* __restrict__ ytr, int64_t ldy, const DevFit& fp, int c,
+                                              int64_t r, int ei) {
   const int e = fp.e0 + fp.es * ei;  // global estimator index (tables, preprocessing view)
   float a0, a1, a2, a3;
   const bool target = (c == fp.G);
-  // the output weights and positional row are loaded before the feature gather's dependent chain
-  // (eF / vcol -> views), so their latency overlaps it
-  float w[3][4], pw[3];
-  {
-    const int cp = target ? 0 : c;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      const int dd = lane + 64 * q;
-      if (!target) {
-        const float4 w4 = *reinterpret_cast<const float4*>(encw + dd * 4);
-        w[q][0] = w4.x; w[q][1] = w4.y; w[q][2] = w4.z; w[q][3] = w4.w;
-      } else {
-        const float2 w2 = *reinterpret_cast<const float2*>(yencw + dd * 2);
-        w[q][0] = w2.x; w[q][1] = w2.y; w[q][2] = w[q][3] = 0.f;
-      }
-      pw[q] = target ? 0.f : pos[cp * 192 + dd];
-    }
-  }
   if (!target) {
     float v[2], ind[2];
     const int Fe = fp.eF[e];
@@ -1618,19 +1586,61 @@ __device__ __forceinline__ void encode_token(int64_t tok, const float* __restric
     }
     a2 = a3 = 0.f;
   }
+  return make_float4(a0, a1, a2, a3);
+}
+// (estimator, row, column) of token tok of [E][R][C]
+template <bool U32>
+__device__ __forceinline__ void encode_split(int64_t tok, int C, int64_t R, const FastDiv& divC, const FastDiv& divR,
+                                             int& c, int64_t& r, int& ei) {
+  if constexpr (U32) {
+    uint32_t cu, ru;
+    const uint32_t rr = divC.divmod((uint32_t)tok, cu);
+    ei = (int)divR.divmod(rr, ru);
+    c = (int)cu;
+    r = ru;
+  } else {
+    c = (int)(tok % C);
+    const int64_t rr = tok / C;
+    r = rr % R;
+    ei = (int)(rr / R);
+  }
+}
+// (encode_expand, the fma chain of one feature: npfn_common.h, shared with k_row_layer)
+template <bool U32>
+__device__ __forceinline__ void encode_token(int64_t tok, const float* __restrict__ ytr, int64_t ldy, int64_t R,
+                                             const DevFit& fp, const float* __restrict__ encw,
+                                             const float* __restrict__ yencw, const float* __restrict__ pos,
+                                             float* __restrict__ resid, bf16_t* __restrict__ resid_bf,
+                                             const FastDiv& divC, const FastDiv& divR) {
+  const int lane = threadIdx.x & 63;
+  int c, ei;
+  int64_t r;
+  encode_split<U32>(tok, fp.C, R, divC, divR, c, r, ei);  // tok is wave-uniform: once per wave
+  const bool target = (c == fp.G);
+  // the output weights and positional row are loaded before the feature gather's dependent chain
+  // (eF / vcol -> views), so their latency overlaps it
+  float w[3][4], pw[3];
+  {
+    const int cp = target ? 0 : c;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      const int dd = lane + 64 * q;
+      if (!target) {
+        const float4 w4 = *reinterpret_cast<const float4*>(encw + dd * 4);
+        w[q][0] = w4.x; w[q][1] = w4.y; w[q][2] = w4.z; w[q][3] = w4.w;
+      } else {
+        const float2 w2 = *reinterpret_cast<const float2*>(yencw + dd * 2);
+        w[q][0] = w2.x; w[q][1] = w2.y; w[q][2] = w[q][3] = 0.f;
+      }
+      pw[q] = target ? 0.f : pos[cp * 192 + dd];
+    }
+  }
+  const float4 a = encode_seed(ytr, ldy, fp, c, r, ei);
   const int64_t base = tok * 192;
 #pragma unroll
   for (int q = 0; q < 3; ++q) {
     const int dd = lane + 64 * q;
-    float o;
-    // explicit fma order: w0 a0 + w1 a1 + w2 a2 + w3 a3 + pos as the contracted expression
-    // evaluates (the first product fused onto the rounded second)
-    const float s01 = __fmaf_rn(w[q][0], a0, w[q][1] * a1);
-    if (!target) {
-      o = __fmaf_rn(w[q][3], a3, __fmaf_rn(w[q][2], a2, s01)) + pw[q];
-    } else {
-      o = s01;
-    }
+    const float o = encode_expand(target, w[q][0], w[q][1], w[q][2], w[q][3], pw[q], a.x, a.y, a.z, a.w);
     resid[base + dd] = o;
     if (resid_bf) resid_bf[base + dd] = f2bf(o);  // null: the fused path (k_row_layer reads resid)
   }
@@ -1650,6 +1660,19 @@ __global__ __launch_bounds__(256) void k_encode(const float* __restrict__ ytr, i
   const int64_t tok = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (tok < (int64_t)fp.E * R * fp.C)
     encode_token<U32>(tok, ytr, ldy, R, fp, encw, yencw, pos, resid, resid_bf, divC, divR);
+}
+
+// The seeds alone, one thread per token: seed [E][R][C] float4 (16 B per token instead of the
+// token's 768 B).  The layer-0 launch of k_row_layer expands them in registers (encode_expand).
+template <bool U32>
+__global__ __launch_bounds__(256) void k_encode_seed(const float* __restrict__ ytr, int64_t ldy, int64_t R, DevFit fp,
+                                                     float4* __restrict__ seed, FastDiv divC, FastDiv divR) {
+  const int64_t tok = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (tok >= (int64_t)fp.E * R * fp.C) return;
+  int c, ei;
+  int64_t r;
+  encode_split<U32>(tok, fp.C, R, divC, divR, c, r, ei);
+  seed[tok] = encode_seed(ytr, ldy, fp, c, r, ei);
 }
 
 // ========================================================== K5 GEMM + epilogues
@@ -3748,6 +3771,17 @@ void launch_encode(const float* ytr, int64_t ldy, int64_t R, const DevFit& fp, c
   else
     hipLaunchKernelGGL(k_encode<false>, dim3(grid), dim3(256), 0, s, ytr, ldy, R, fp, encw, yencw, pos, resid, resid_bf,
                        FastDiv(), FastDiv());
+}
+void launch_encode_seed(const float* ytr, int64_t ldy, int64_t R, const DevFit& fp, float* seed, hipStream_t s) {
+  const int64_t tokens = (int64_t)fp.E * R * fp.C;
+  if (tokens <= 0) return;
+  const unsigned grid = (unsigned)blocks_for(tokens, 256);
+  if (tokens < (int64_t(1) << 32) && R < (int64_t(1) << 32))
+    hipLaunchKernelGGL(k_encode_seed<true>, dim3(grid), dim3(256), 0, s, ytr, ldy, R, fp, (float4*)seed,
+                       FastDiv((uint32_t)fp.C), FastDiv((uint32_t)R));
+  else
+    hipLaunchKernelGGL(k_encode_seed<false>, dim3(grid), dim3(256), 0, s, ytr, ldy, R, fp, (float4*)seed, FastDiv(),
+                       FastDiv());
 }
 static constexpr size_t kGemmSmem = 2 * (64 * 64 + 192 * 64) * sizeof(bf16_t);  // 64 KiB
 // decoder-head rows per wave: 32 (8 waves per 128-row tile) or 64 (4 waves, 4 A + 6 B fragment

@@ -16,7 +16,8 @@
 // registers) and the train side stores q and k as soon as they are complete.
 // LDS (160 KB): a 2-slot weight ring (the chunk period is twice a 16-slot kernel's, so one chunk
 // of DMA lead is the same time as the 16-slot kernel's two) + the head-pair feature-attention images for 256
-// slots + LayerNorm parameters.
+// slots + LayerNorm parameters (+ the encoder's tables in a layer-0 entry launch, which expands the
+// tokens from k_encode_seed's 16-byte seeds instead of loading them: ENC_OFF below).
 #include "npfn_common.h"
 #include "npfn_kernels.h"
 #include "npfn_gelu16.h"
@@ -46,7 +47,10 @@ constexpr int VV_OFF = QH_OFF + 2 * KH_ELEMS * 2;    // values: bf16 [RTP][64] (
 constexpr int FA_END = VV_OFF + RTP * 64 * 2;
 constexpr int LNP_OFF = FA_END;                      // float [6][192]: ln2 g,b | ln3 g,b | ln1 g,b
 constexpr int TILE_OFF = LNP_OFF + 6 * 192 * 4;      // int [2]: this / the next tile (dynamic schedule)
-constexpr int SMEM_BYTES = TILE_OFF + 16;
+// Fused encoder (layer-0 entry, rows of <= 64 tokens): yencw [192][2] f32 here; encw [192][4] f32
+// takes the ln2 / ln3 slots of LNP, which a launch without a post part never reads
+constexpr int ENC_OFF = TILE_OFF + 16;
+constexpr int SMEM_BYTES = ENC_OFF + 192 * 2 * 4;
 constexpr int GLDS_PER_WAVE = 3;                     // 1 KB LDS-DMA pieces per wave per chunk
 static_assert(SMEM_BYTES <= 160 * 1024, "LDS budget");
 
@@ -687,14 +691,22 @@ __device__ __forceinline__ void row_layer_body(const RowLayerParams& P, char* sm
             TILE_OFF, -1, 0u};
   const float* lnp = reinterpret_cast<const float*>(smem + LNP_OFF);
 
+  // the layer-0 entry expands the tokens from their seeds (encode_seed / encode_expand of
+  // npfn_kernels.hip) instead of reading them from resid
+  constexpr bool ENC = !POST && !LONG;
+  const bool enc = ENC && P.encw != nullptr;
   ring.issue(0);
   ring.issue(1);
   if (tid < 288) {
     const int a = tid / 48, o = (tid - a * 48) * 4;
     const float* src = a == 0 ? P.ln2g : a == 1 ? P.ln2b : a == 2 ? P.ln3g : a == 3 ? P.ln3b : a == 4 ? P.ln1g : P.ln1b;
+    if (enc && a < 4) src = P.encw + a * 192;  // floats [4 tid, 4 tid + 4): encw row tid
     f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
     if (src) v = *reinterpret_cast<const f32x4*>(src + o);
     *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(smem + LNP_OFF) + a * 192 + o) = v;
+  } else if (enc && tid < 288 + 96) {
+    const int o = (tid - 288) * 4;
+    *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(smem + ENC_OFF) + o) = *reinterpret_cast<const f32x4*>(P.yencw + o);
   }
   for (int i = tid; i < (FA_END - KH_OFF) / 16; i += 512)
     *reinterpret_cast<uint4*>(smem + KH_OFF + 16 * i) = make_uint4(0, 0, 0, 0);
@@ -751,10 +763,50 @@ __device__ __forceinline__ void row_layer_body(const RowLayerParams& P, char* sm
     // the loads need no per-slot branches
     const int lo[2] = {tv[0] ? to[0] : g4 * 4, tv[1] ? to[1] : g4 * 4};
     Acc x[2];
+    if (ENC && enc) {
+      // x[b][f][i] = feature 16f + 4g4 + i of the slot's token by k_encode's encode_expand (bit for
+      // bit its tokens), x holding the positional value first; the positional row comes from global memory (C x 768 B, cache-resident)
+      // (the lane's quarter through an opaque move: its table offsets are then computed here, once
+      // per tile, instead of being hoisted into registers that stay live -- and spill -- all kernel)
+      int g4e;
+      asm volatile("v_mov_b32 %0, %1" : "=v"(g4e) : "v"(g4));
+      const float* ew = reinterpret_cast<const float*>(smem + LNP_OFF) + g4e * 16;
+      const float* yw = reinterpret_cast<const float*>(smem + ENC_OFF) + g4e * 8;
+      const float* const seedb = sg.seed + tok0 * 4;  // uniform bases + 32-bit lane offsets, as below
+      f32x4 sa[2];
+      bool tg[2];
 #pragma unroll
-    for (int b = 0; b < 2; ++b)
+      for (int b = 0; b < 2; ++b) {
+        const int t = tv[b] ? th[b] : 0;
+        const int c = t % C;
+        tg[b] = c == sg.G;
+        sa[b] = *reinterpret_cast<const f32x4*>(seedb + t * 4);
+        const int po = (tg[b] ? 0 : c) * 192 + g4e * 4;
 #pragma unroll
-      for (int f = 0; f < 12; ++f) x[b][f] = *reinterpret_cast<const f32x4*>(rbase + lo[b] + f * 16);
+        for (int f = 0; f < 12; ++f) x[b][f] = *reinterpret_cast<const f32x4*>(P.pos + po + f * 16);
+      }
+#pragma unroll
+      for (int f = 0; f < 12; ++f) {
+        const f32x4 y01 = *reinterpret_cast<const f32x4*>(yw + f * 32);
+        const f32x4 y23 = *reinterpret_cast<const f32x4*>(yw + f * 32 + 4);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const f32x4 w = *reinterpret_cast<const f32x4*>(ew + f * 64 + i * 4);
+          const float y0 = i < 2 ? y01[2 * i] : y23[2 * i - 4], y1 = i < 2 ? y01[2 * i + 1] : y23[2 * i - 3];
+#pragma unroll
+          for (int b = 0; b < 2; ++b) {
+            x[b][f][i] = encode_expand(tg[b], tg[b] ? y0 : w[0], tg[b] ? y1 : w[1], w[2], w[3], x[b][f][i], sa[b][0],
+                                       sa[b][1], sa[b][2], sa[b][3]);
+          }
+        }
+        sched_fence();  // one feature block's weights live at a time (the max-ILP scheduler hoists every read)
+      }
+    } else {
+#pragma unroll
+      for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int f = 0; f < 12; ++f) x[b][f] = *reinterpret_cast<const f32x4*>(rbase + lo[b] + f * 16);
+    }
 
     Frag xb[2];
     if constexpr (POST) {
