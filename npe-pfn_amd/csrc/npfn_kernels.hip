@@ -268,6 +268,9 @@ __global__ __launch_bounds__(256) void k_quantile_fit(const float* __restrict__ 
     return;
   }
   for (int i = tid; i < nq; i += 256) {
+    // numpy rounds (cnt - 1) * pq before taking its fraction, and dba * g before adding it: a fused
+    // multiply-add gives g = 3e-15 where numpy's is 0, which breaks up a run of repeated quantiles
+#pragma clang fp contract(off)
     const double pq = (qt_ref(i, nq) * 100.0) / 100.0;       // percentile(ref*100) / 100
     const double vi = (double)(cnt - 1) * pq;
     const double pf = floor(vi);
