@@ -412,21 +412,6 @@ int upload_f32(npfn_engine* h, const float* src, size_t n, float** dst) {
   return NPFN_OK;
 }
 
-// a row-kernel weight stream: chunk c (192 x 64 values) as fp16 where f16[c] (NPFN_GELU_F16: the
-// W2 chunks), else bf16
-int upload_stream(npfn_engine* h, const std::vector<float>& img, const std::vector<uint8_t>& f16, bf16_t** dst) {
-  const size_t n = img.size(), ce = 192 * 64;
-  std::vector<uint16_t> tmp(n);
-  for (size_t i = 0; i < n; ++i)
-    tmp[i] = f16[i / ce] ? __builtin_bit_cast(uint16_t, (_Float16)img[i]) : host_f2bf(img[i]);
-  void* p = nullptr;
-  HIPCHK(hipMalloc(&p, n * sizeof(uint16_t)));
-  h->weight_allocs.push_back(p);
-  HIPCHK(hipMemcpy(p, tmp.data(), n * sizeof(uint16_t), hipMemcpyHostToDevice));
-  *dst = (bf16_t*)p;
-  return NPFN_OK;
-}
-
 int upload_bf16(npfn_engine* h, const float* src, size_t n, bf16_t** dst) {
   std::vector<uint16_t> tmp(n);
   for (size_t i = 0; i < n; ++i) tmp[i] = host_f2bf(src[i]);
@@ -486,8 +471,6 @@ int build_rowk_streams(npfn_engine* h, const std::vector<RowkHost>& hw) {
   const int L = (int)hw.size(), d = h->cfg.d_model, dff = h->cfg.d_ff, ns = dff / 64;
   for (int j = 0; j <= L; ++j) {
     std::vector<float> img;
-    std::vector<uint8_t> f16;  // per chunk: stored as fp16 (the W2 chunks under NPFN_GELU_F16)
-    auto mark = [&](bool h16) { f16.resize(img.size() / (192 * 64), 0); f16.back() = h16 ? 1 : 0; };
     if (j >= 1) {
       const RowkHost& w = hw[j - 1];
       for (int kc = 0; kc < 3; ++kc) chunk_image(img, w.item_out.data(), d, false, 0, 64 * kc);
@@ -495,10 +478,8 @@ int build_rowk_streams(npfn_engine* h, const std::vector<RowkHost>& hw) {
       for (int s = 1; s < ns; ++s) {
         chunk_image(img, w.w1.data(), d, true, 64 * s, 0);
         chunk_image(img, w.w2.data(), dff, false, 0, 64 * (s - 1));
-        mark(NPFN_GELU_F16 != 0);
       }
       chunk_image(img, w.w2.data(), dff, false, 0, 64 * (ns - 1));
-      mark(NPFN_GELU_F16 != 0);
     }
     const int post = (int)(img.size() / (192 * 64));
     if (j < L) {
@@ -512,9 +493,8 @@ int build_rowk_streams(npfn_engine* h, const std::vector<RowkHost>& hw) {
       for (int m = 0; m < 3; ++m)  // item q | k | v (the test side stops after q)
         for (int kc = 0; kc < 3; ++kc) chunk_image(img, w.item_qkv.data(), d, false, (size_t)m * d, 64 * kc);
     }
-    f16.resize(img.size() / (192 * 64), 0);
     bf16_t* dptr = nullptr;
-    RCHK_(upload_stream(h, img, f16, &dptr));
+    RCHK_(upload_bf16(h, img.data(), img.size(), &dptr));
     h->rowk_stream.push_back(dptr);
     h->rowk_post.push_back(post);
   }
@@ -1423,12 +1403,7 @@ Fit* step_fit(npfn_engine* h, int k) { return h->fit_token != 0 ? &h->cur->slots
 // stream's test-side launches.  prep_done[k] = step
 // k's fit is complete.  `piped` = whether that happened (no fit token: fit0 is refitted in
 // order on the main stream).
-// A/B switch: NPFN_TRAIN_AHEAD=<steps> (default 2)
-static const int kTrainAhead = [] {
-  const char* e = getenv("NPFN_TRAIN_AHEAD");
-  const int v = e ? atoi(e) : 2;
-  return v < 0 ? 0 : v;  // 0: every train forward in order on the main stream
-}();
+constexpr int kTrainAhead = 2;
 int ar_side_train(npfn_engine* h, const float* joint, int Ft, int64_t n, int F, int k) {
   hipStream_t t = h->side_t;
   h->side_busy = true;
@@ -1448,8 +1423,7 @@ int ar_prefit(npfn_engine* h, const float* joint, int Ft, int64_t n, int dx, int
   piped = false;
   // while the live profiler is on, the fits run in order on the main stream: an event pair
   // then times its launch alone, not the launch plus whatever shared the CUs with it
-  static const bool serial = [] { const char* e = getenv("NPFN_SERIAL_FITS"); return e && e[0] == '1'; }();  // A/B
-  if (h->fit_token == 0 || dth < 2 || h->prof.on || serial) return NPFN_OK;
+  if (h->fit_token == 0 || dth < 2 || h->prof.on) return NPFN_OK;
   if (!h->side) {
     int least = 0, greatest = 0;
     HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
@@ -1498,10 +1472,6 @@ int ar_step_fit(npfn_engine* h, const float* joint, int Ft, int64_t n, int dx, i
                 hipStream_t s) {
   if (!piped) return fit_impl(h, joint, Ft, joint + dx + k, Ft, n, dx + k, s);
   if (k == 0) return NPFN_OK;  // fitted on s by ar_prefit
-  if (kTrainAhead == 0) {
-    HIPCHK(hipStreamWaitEvent(s, h->stat_done[k], 0));
-    return fit_train(h, joint, Ft, joint + dx + k, Ft, n, s);
-  }
   HIPCHK(hipStreamWaitEvent(s, h->prep_done[k], 0));
   if (k + kTrainAhead < dth) RCHK(ar_side_train(h, joint, Ft, n, dx + k + kTrainAhead, k + kTrainAhead));
   return NPFN_OK;
@@ -1870,8 +1840,6 @@ int npfn_engine_create(const npfn_config* cfg, const float* weights, size_t n_we
     h->enc_fused = !(ef && ef[0] == '0');
     const char* dt = getenv("NPFN_ROWK_STATIC");
     h->dyn_tiles = !(dt && dt[0] == '1');
-    const char* cr = getenv("NPFN_CHUNK_ROWS");  // A/B: query rows per forward chunk (npfn_set_chunk_rows)
-    if (cr && atoll(cr) > 0) h->chunk_rows = atoll(cr);
     if (hipMalloc((void**)&h->tile_ctrs, npfn_engine::kTileCtrs * sizeof(unsigned)) == hipSuccess)
       (void)hipMemset(h->tile_ctrs, 0, npfn_engine::kTileCtrs * sizeof(unsigned));
     else

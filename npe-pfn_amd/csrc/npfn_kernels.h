@@ -121,12 +121,9 @@ struct RowSeg {
   const float* seed;
   int G;
 };
-// NPFN_GELU_F16: the row kernel's MLP hidden slabs go to W2 as fp16 B fragments from a packed-f16
-// GELU (v_pk_*_f16), and the W2 chunk images of the weight stream are fp16 (v_mfma_f32_16x16x32_f16);
-// 0: GELU in f32, bf16 fragments and W2 images (npfn_rowk2.hip run_w2_gelu)
-#ifndef NPFN_GELU_F16
-#define NPFN_GELU_F16 0
-#endif
+// (measured r06, code in git history: the MLP hidden slabs as fp16 B fragments from a packed-f16
+// GELU with fp16 W2 chunk images made k_row_layer 194.68 vs 194.87 ms, -0.1 %,
+// profiles/r06/ab_gelu16_r06g.txt; the GELU stays in f32 with bf16 fragments and W2 images)
 struct RowLayerParams {
   int64_t R;               // rows per estimator: a tile never spans two estimators, so a
                            // row's tile position (and its result, bit for bit) does not

@@ -1510,9 +1510,6 @@ __global__ __launch_bounds__(256) void k_target_tf(const float* __restrict__ y, 
 // per token) and k_row_layer's layer-0 launch applies encode_expand in registers (npfn_rowk2.hip).
 // U32: the launch's tokens < 2^32, so (estimator, row, token) come from FastDiv (the 64-bit
 // divisions bound the kernel: r04 ran it at ~2 TB/s of stores); else 64-bit division.
-#ifndef NPFN_ENC_SPEC  // 1: feature loads ahead of Fe (r05: k_encode 3.53 -> 3.37 ms, bitwise equal,
-#define NPFN_ENC_SPEC 1  // profiles/r05/ab_encode_spec_r05bd.txt); 0: loads behind the j < Fe test
-#endif
 // encode_seed: everything of a token up to the four scalars a0..a3 that decide its 192 values
 // (view gather, NaN / +-inf indicators, clamping, group scale; the target / classifier branches).
 // (c, r, ei): the token's column, row and estimator of the group -- wave-uniform in k_encode,
@@ -1525,9 +1522,10 @@ __device__ __forceinline__ float4 encode_seed(const float* __restrict__ ytr, int
   if (!target) {
     float v[2], ind[2];
     const int Fe = fp.eF[e];
-#if NPFN_ENC_SPEC
     // the feature loads are issued before Fe is known (index clamped into the tables, the
     // view column into the row), so the chain is (eF | vcol, mu, sd) -> views, not eF -> vcol -> views
+    // (measured r05 against loads behind the j < Fe test: k_encode 3.53 -> 3.37 ms, bitwise equal,
+    // profiles/r05/ab_encode_spec_r05bd.txt; that form is in git history)
     float xs[2], ms[2], ss[2];
     {
       const int64_t eb = (int64_t)e * fp.Fmax;
@@ -1540,21 +1538,14 @@ __device__ __forceinline__ float4 encode_seed(const float* __restrict__ ytr, int
         ss[q] = fp.sd[eb + jj];
       }
     }
-#endif
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       const int j = 2 * c + q;
       v[q] = 0.f; ind[q] = 0.f;
       if (j < Fe) {
-#if NPFN_ENC_SPEC
         float x = xs[q];
         const float m = ms[q];
         const float s = ss[q];
-#else
-        float x = fp.views[r * fp.Vw + fp.vcol[(int64_t)e * fp.Fmax + j]];
-        const float m = fp.mu[(int64_t)e * fp.Fmax + j];
-        const float s = fp.sd[(int64_t)e * fp.Fmax + j];
-#endif
         if (!isfinite(x)) {
           ind[q] = isnan(x) ? -2.0f : (x > 0.f ? 2.0f : 4.0f);
           x = m;
@@ -1684,19 +1675,13 @@ __global__ __launch_bounds__(256) void k_encode_seed(const float* __restrict__ y
 // register-staged double-buffered LDS with a 16-byte XOR swizzle.
 // MT = rows per tile: 64 (4 waves) or 128 (8 waves, the decoder head: half the weight-tile
 // traffic per flop).  Waves tile the block as (MT/32) x 2 of 32 x 96.
-#ifndef NPFN_GEMM_STAGED
-#define NPFN_GEMM_STAGED 1
-#endif
-constexpr bool kGemmStagedF32 = NPFN_GEMM_STAGED != 0;
-// WM = rows per wave (32, or 64 for the decoder head: 4 A + 6 B fragment reads per 24 MFMAs
-// instead of 2 + 6 per 12 -- the same per-element K order, so the same bits).
-template <int EPI, int MT = 64, int WM = 32>
-__global__ __launch_bounds__((MT / WM) * 128) void k_gemm(const bf16_t* __restrict__ A, int64_t lda,
+template <int EPI, int MT = 64>
+__global__ __launch_bounds__((MT / 32) * 128) void k_gemm(const bf16_t* __restrict__ A, int64_t lda,
                                                           const bf16_t* __restrict__ W, int64_t M, int N, int K,
                                                           EpiParams p) {
   static_assert(MT == 64 || MT == 128 || MT == 256, "k_gemm: MT must be 64, 128 or 256");
-  static_assert(WM == 32 || WM == 64, "k_gemm: WM must be 32 or 64");
-  static_assert(EPI != EPI_LN || (MT == 64 && WM == 32), "k_gemm: the LayerNorm epilogue assumes 64-row tiles");
+  static_assert(EPI != EPI_LN || MT == 64, "k_gemm: the LayerNorm epilogue assumes 64-row tiles");
+  constexpr int WM = 32;                         // rows per wave
   constexpr int NT = (MT / WM) * 128;            // threads: (MT / WM) x 2 waves
   constexpr int IM = WM / 16;                    // 16-row MFMA blocks per wave
   constexpr int NA = MT * 8 / NT;                // A-tile uint4 per thread (MT rows x 8)
@@ -1817,7 +1802,7 @@ __global__ __launch_bounds__((MT / WM) * 128) void k_gemm(const bf16_t* __restri
         p.resid_bf[gm * 192 + col] = f2bf(o);
       }
     }
-  } else if (EPI == EPI_LOGIT && MT >= 128 && kGemmStagedF32) {
+  } else if (EPI == EPI_LOGIT && MT >= 128) {
     // decoder logits: the accumulators go through LDS in two 64-row halves so that every
     // store is a 16-byte piece of a contiguous 768-byte row segment (the MFMA layout would
     // store 4-byte columns of 4 rows per instruction)
@@ -2420,10 +2405,6 @@ __device__ __forceinline__ float block_reduce_max(float v, float* red) {
 // and sum come from one merged (max, sum) reduction behind a single barrier, and every
 // thread accumulates its probabilities in registers: HBM-streaming, E barriers per row.
 constexpr int kMixV4 = 8;
-#ifndef NPFN_MIX_HOIST
-#define NPFN_MIX_HOIST 1
-#endif
-constexpr bool kMixHoist = NPFN_MIX_HOIST != 0;
 
 __device__ __forceinline__ void ms_merge(float& m, float& s, float m2, float s2) {
   const float M = fmaxf(m, m2);
@@ -2482,14 +2463,14 @@ __device__ void mix_row_fast(const logit_t* __restrict__ logits, int64_t R, int6
   f32x4 acc[NV];
 #pragma unroll
   for (int j = 0; j < NV; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  // NPFN_MIX_HOIST: the translation entries of the thread's borders b0 .. b0 + PB loaded once
-  // for all the row's translated estimators (they depend on the fit only; +42 VGPRs, 2 instead
-  // of 4 resident blocks per CU), else read per translated estimator
-  TransEntry te[kMixHoist ? 4 * NV + 1 : 1];
+  // the translation entries of the thread's borders b0 .. b0 + PB loaded once for all the row's
+  // translated estimators (they depend on the fit only; +42 VGPRs, 2 instead of 4 resident blocks
+  // per CU), not read per translated estimator
+  TransEntry te[4 * NV + 1];
   // the thread's border-repair cancel flags (4 bytes per float4), fit-only too: loaded once, not per
   // translated estimator (r05: k_mix_sample 7.03 -> 6.50 ms, profiles/r05/ab_mix_cancel_hoist_r05az.txt)
   uint32_t cmask[NV];
-  if (kMixHoist && tr.ett != nullptr) {
+  if (tr.ett != nullptr) {
 #pragma unroll
     for (int k = 0; k <= 4 * NV; ++k) {
       const int b = b0 + k;
@@ -2527,7 +2508,7 @@ __device__ void mix_row_fast(const logit_t* __restrict__ logits, int64_t R, int6
       if (j < nv && b < nb) {
         v[j] = v[j] * invT;
         if (trans) {
-          const uint32_t cm = kMixHoist ? cmask[j] : *reinterpret_cast<const uint32_t*>(tr.tcancel + b);
+          const uint32_t cm = cmask[j];
 #pragma unroll
           for (int i = 0; i < 4; ++i)
             if ((cm >> (8 * i)) & 0xffu) v[j][i] = -INFINITY;
@@ -2615,15 +2596,14 @@ __device__ void mix_row_fast(const logit_t* __restrict__ logits, int64_t R, int6
     }
     __syncthreads();
     const float invE = 1.0f / (float)E;
-    float left = trans_left_e(pc, kMixHoist ? te[0] : tr.tab[min(b0, nb)], min(b0, nb), nb);
+    float left = trans_left_e(pc, te[0], min(b0, nb), nb);
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
       const int b = b0 + 4 * j;
       if (j < nv && b < nb)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          const float right = trans_left_e(pc, kMixHoist ? te[(4 * j + i + 1) % (kMixHoist ? 4 * NV + 1 : 1)]
-                                                         : tr.tab[b + i + 1], b + i + 1, nb);
+          const float right = trans_left_e(pc, te[4 * j + i + 1], b + i + 1, nb);
           const float q = fmaxf(right - left, 0.f);
           acc[j][i] += (tr.geo ? __logf(q) : q) * invE;
           left = right;
@@ -3787,13 +3767,11 @@ void launch_encode_seed(const float* ytr, int64_t ldy, int64_t R, const DevFit& 
                        FastDiv());
 }
 static constexpr size_t kGemmSmem = 2 * (64 * 64 + 192 * 64) * sizeof(bf16_t);  // 64 KiB
-// decoder-head rows per wave: 32 (8 waves per 128-row tile) or 64 (4 waves, 4 A + 6 B fragment
-// reads per 24 MFMAs instead of 2 + 6 per 12).  r06, bitwise equal: WM 64 7.30 ms, WM 64 on
-// 256-row tiles 8.57 ms, against 6.66 ms per c2 call at 32 (profiles/r06/ab_decoder_wm64_r06s.txt):
-// the head GEMM is not bound by its LDS reads; the occupancy the wider wave tile costs is what counts
-#ifndef NPFN_DEC_WM
-#define NPFN_DEC_WM 32
-#endif
+// decoder-head rows per wave: 32 (8 waves per 128-row tile).  Measured r06, code in git history:
+// 64 rows per wave (4 waves, 4 A + 6 B fragment reads per 24 MFMAs instead of 2 + 6 per 12), bitwise
+// equal, was 7.30 ms, and 8.57 ms on 256-row tiles, against 6.66 ms per c2 call at 32
+// (profiles/r06/ab_decoder_wm64_r06s.txt): the head GEMM is not bound by its LDS reads; the occupancy
+// the wider wave tile costs is what counts
 #ifndef NPFN_DEC_MT
 #define NPFN_DEC_MT 128
 #endif
@@ -3803,19 +3781,11 @@ void gemm_setup() {
                             kFeatAttnMaxC * 576 * sizeof(bf16_t));
   (void)hipFuncSetAttribute((const void*)k_feat_attn_wide, hipFuncAttributeMaxDynamicSharedMemorySize,
                             kWideMaxC * 64 * sizeof(bf16_t));
-  (void)hipFuncSetAttribute((const void*)k_gemm<EPI_LOGIT, NPFN_DEC_MT, NPFN_DEC_WM>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, kGemmSmem128);
   (void)hipFuncSetAttribute((const void*)k_gemm<EPI_LOGIT, NPFN_DEC_MT>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             kGemmSmem128);
   (void)hipFuncSetAttribute((const void*)k_gemm<EPI_BF16>, hipFuncAttributeMaxDynamicSharedMemorySize, kGemmSmem);
   (void)hipFuncSetAttribute((const void*)k_gemm<EPI_BF16_GELU>, hipFuncAttributeMaxDynamicSharedMemorySize, kGemmSmem);
-  (void)hipFuncSetAttribute((const void*)k_gemm<EPI_LOGIT>, hipFuncAttributeMaxDynamicSharedMemorySize, kGemmSmem);
   (void)hipFuncSetAttribute((const void*)k_gemm<EPI_LN>, hipFuncAttributeMaxDynamicSharedMemorySize, kGemmSmem);
-}
-// decoder-head tile size: 128 rows unless NPFN_GEMM_MT64=1 (A/B switch)
-static bool gemm_mt128() {
-  static const bool v = [] { const char* e = getenv("NPFN_GEMM_MT64"); return !(e && e[0] == '1'); }();
-  return v;
 }
 void launch_gemm(int epi, const bf16_t* A, int64_t lda, const bf16_t* W, int64_t M, int N, int K,
                  const EpiParams& p, hipStream_t s) {
@@ -3823,15 +3793,12 @@ void launch_gemm(int epi, const bf16_t* A, int64_t lda, const bf16_t* W, int64_t
   switch (epi) {
     case EPI_BF16: hipLaunchKernelGGL(k_gemm<EPI_BF16>, grid, dim3(256), kGemmSmem, s, A, lda, W, M, N, K, p); break;
     case EPI_BF16_GELU: hipLaunchKernelGGL(k_gemm<EPI_BF16_GELU>, grid, dim3(256), kGemmSmem, s, A, lda, W, M, N, K, p); break;
-    case EPI_LOGIT:
-      if (gemm_mt128()) {
-        dim3 g128(blocks_for(M, NPFN_DEC_MT), grid.y);
-        hipLaunchKernelGGL((k_gemm<EPI_LOGIT, NPFN_DEC_MT, NPFN_DEC_WM>), g128, dim3((NPFN_DEC_MT / NPFN_DEC_WM) * 128),
-                           kGemmSmem128, s, A, lda, W, M, N, K, p);
-      } else {
-        hipLaunchKernelGGL(k_gemm<EPI_LOGIT>, grid, dim3(256), kGemmSmem, s, A, lda, W, M, N, K, p);
-      }
+    case EPI_LOGIT: {  // the decoder head: NPFN_DEC_MT-row tiles
+      dim3 g128(blocks_for(M, NPFN_DEC_MT), grid.y);
+      hipLaunchKernelGGL((k_gemm<EPI_LOGIT, NPFN_DEC_MT>), g128, dim3((NPFN_DEC_MT / 32) * 128), kGemmSmem128, s, A,
+                         lda, W, M, N, K, p);
       break;
+    }
     case EPI_LN: hipLaunchKernelGGL(k_gemm<EPI_LN>, grid, dim3(256), kGemmSmem, s, A, lda, W, M, N, K, p); break;
   }
 }

@@ -150,9 +150,6 @@ SIGNATURES = {
 }
 
 _LIB = None
-# A/B switch (tools/ab_bench.py): NPFN_NO_REPEATED=1 runs repeated query rows through the
-# plain npfn_ar_sample / npfn_ar_log_prob (step 0 over every row)
-_NO_REPEATED = os.environ.get("NPFN_NO_REPEATED") == "1"
 
 
 class EngineError(RuntimeError):
@@ -757,7 +754,7 @@ class Engine:
         self.check_table(n, dx + dth - 1)
         theta = torch.empty((N, dth), dtype=torch.float32, device=self.device)
         lp = torch.empty(N, dtype=torch.float32, device=self.device) if with_log_prob else None
-        if x_unique is not None and not _NO_REPEATED:
+        if x_unique is not None:
             x_unique, U = self._ar_unique("ar_sample", x_unique, N, dx)
             _check(self.lib, self.lib.npfn_ar_sample_repeated(
                 self.h, _ptr(x_ctx), _ptr(theta_ctx), n, dx, dth, _ptr(x_unique), U, N, int(counter), int(row_base),
@@ -838,7 +835,7 @@ class Engine:
             raise ValueError("ar_log_prob: theta shape mismatch")
         self.check_table(n, dx + dth - 1)
         out = torch.empty(N, dtype=torch.float32, device=self.device)
-        if x_unique is not None and not _NO_REPEATED:
+        if x_unique is not None:
             x_unique, U = self._ar_unique("ar_log_prob", x_unique, N, dx, of=False)
             _check(self.lib, self.lib.npfn_ar_log_prob_repeated(
                 self.h, _ptr(x_ctx), _ptr(theta_ctx), n, dx, dth, _ptr(x_unique), U, _ptr(theta), N, _ptr(out),
